@@ -1,6 +1,6 @@
 """Benchmark: train interactions/s, MF-BPR dim=64, MovieLens-20M-shaped, 1 -> 8 MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -33,10 +33,22 @@ at W-rank geometry on ONE GPU (global batch W*B, the global draw, U/W users, eve
 with the collectives replaced by same-size local copies (comm.LocalComm).
 
 Rank 0 prints ONE JSON line.  `value` = positives processed by all ranks / the
-max over ranks of the timed wall time.  `roofline` is for the dominant kernel
-(rg_mf_apply_prepare: the dense optimizer pass + the next step's prepare), timed
-with HIP events on the stream it is launched on; `cpu_baseline` times the CPU restatement (oracle/, the
-reference's algorithm incl. its random.choices sampler) on a bounded sample.
+max over ranks of the timed wall time; `ms_per_step` = that wall time / --steps.  `roofline`
+is for the dominant kernel (rg_mf_apply_prepare: the dense optimizer pass + the next step's
+prepare), timed with HIP events recorded inside the timed steps on the stream it is launched on.
+
+A plain run sets up, warms up, times the steps, writes its outputs (--dump-outputs) and prints
+the line.  Everything that takes work of its own is behind `--full`: `cpu_baseline` (the CPU
+restatement, oracle/, the reference's algorithm incl. its random.choices sampler, on a bounded
+sample; --no-cpu-baseline leaves it out of a --full run), the measured plan build
+(`plan_build_*`), the STREAM-copy ceiling and the PMC traffic beside the roofline, and the lazy
+pass's row counts (`lazy_dense_pass`, with the roofline that needs them).
+
+`--dump-outputs DIR` writes what the timed path's last step left its caller as DIR/<name>.npy
+(float32 / float64): the four tables and the loss (MF), every parameter and the loss (NCF,
+NeuMF), the iterations' returned losses and slates (cGAN), the metrics (eval).  At most 64 MiB:
+a larger set keeps a fixed, seeded sample of the elements of its big arrays.  Data, tables and
+the sampler's state are seeded, so two runs with the same arguments have the same inputs.
 """
 import argparse
 import contextlib
@@ -92,7 +104,13 @@ def parse():
     ap.add_argument("--optim", default="adam")
     ap.add_argument("--zipf", type=float, default=1.0)
     ap.add_argument("--cpu-baseline-seconds", type=float, default=15.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline, the plan build, "
+                         "the STREAM-copy ceiling and PMC traffic of the roofline, the lazy pass's row counts")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last step computed (tables, parameters, losses) as "
+                         "DIR/<name>.npy, float32 / float64, at most 64 MiB (a seeded sample of a larger set)")
     ap.add_argument("--no-prefetch", action="store_true")
     ap.add_argument("--model", default="mf", choices=["mf", "ncf", "neumf", "gan", "eval"],
                     help="mf: the BASELINE metric (MF-BPR); ncf: config 3 (NCF MLP, MFMA roofline); "
@@ -128,6 +146,29 @@ def parse():
                          "all ahead; the step time is then taken by events after the spin (GPU-side time only, "
                          "reported as gpu_ahead_us_per_step; not the driver's line)")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, rank=0, world=1):
+    """--dump-outputs: each named tensor / array to DIR/<name>.npy (DIR/<name>.rank<r>.npy with
+    several ranks), float32 kept, anything else as float64.  Over DUMP_LIMIT_BYTES in all, the
+    arrays above 1 MiB keep the same fraction of their elements each, at sorted flat indices
+    drawn without replacement from RandomState(0) (the same indices in every run)."""
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        host[name] = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+    big = sum(a.nbytes for a in host.values() if a.nbytes > (1 << 20))
+    small = sum(a.nbytes for a in host.values()) - big
+    frac = 1.0 if big + small <= DUMP_LIMIT_BYTES else (DUMP_LIMIT_BYTES - small) / big
+    rs = np.random.RandomState(0)
+    for name, a in host.items():
+        if frac < 1.0 and a.nbytes > (1 << 20):
+            a = a.reshape(-1)[np.sort(rs.choice(a.size, int(a.size * frac), replace=False))]
+        np.save(os.path.join(dirname, name + (f".rank{rank}" if world > 1 else "") + ".npy"), a)
 
 
 def cpu_baseline(data, d, B, n, loss, budget_s):
@@ -322,7 +363,11 @@ def bench_ncf(args):
         out["ms_per_step"] = out["gpu_ahead_us_per_step"] * 1e-3
         out["value"] = B * world / (out["gpu_ahead_us_per_step"] * 1e-6)
         out["timing"] = "GPU events after a host-ahead spin (diagnostic)"
-    if not args.no_cpu_baseline and world == 1:
+    if args.dump_outputs:
+        arrays = {f"param_{k:02d}_{nm.replace('.', '_')}": p for k, (nm, p) in enumerate(zip(names, eng.params()))}
+        arrays["loss"] = eng.loss_out[:1]
+        dump_outputs(args.dump_outputs, arrays, rank, world)
+    if args.full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = ncf_cpu_baseline([p.clone() for p in params], names, data, B, n, neumf,
                                                args.cpu_baseline_seconds)
     if rank == 0:
@@ -464,11 +509,13 @@ def bench_gan(args):
     del G, D
     steps = max(5, args.steps // 5 * 5)
 
+    last = {}
+
     def step(k):
         bt = batches[k % nb]
-        eng.d_step(bt)
+        last["d_out"] = eng.d_step(bt)
         if (k + 1) % 5 == 0:
-            eng.g_step(bt, slates=True)
+            last["g_loss"], last["g_slates"] = eng.g_step(bt, slates=True)
 
     for k in range(args.warmup):
         step(k)
@@ -481,6 +528,8 @@ def bench_gan(args):
     b_.record()
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
+    if args.dump_outputs:      # the returns of the last D iteration and the last G iteration
+        dump_outputs(args.dump_outputs, last)
     ms_ev = a.elapsed_time(b_)
     fd, fg = gan_flops(N, S, H, E, Z, B)
     flops = steps * fd + steps // 5 * fg
@@ -513,7 +562,7 @@ def bench_gan(args):
                         "frac_rule": "max(flop time at the fp32 MFMA peak, byte time at the HBM peak) / measured"},
            "cpu_baseline": None,
            "final": [float(x) for x in eng.d_step(batches[0]).cpu()]}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = gan_cpu_baseline(g_sd, d_sd, np_batches, N, S, H, E, Z, args.cpu_baseline_seconds)
     print(json.dumps(out), flush=True)
 
@@ -572,7 +621,9 @@ def bench_eval(args):
            "config": {"workload": f"rank {I} items per test user, top {k}, two metric passes", "embedding_dim": d,
                       "parallelism": "dp1"},
            "precision": float(p), "recall": float(r), "map": float(mp), "roofline": None, "cpu_baseline": None}
-    if not args.no_cpu_baseline:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"precision": p, "recall": r, "map": mp})
+    if args.full and not args.no_cpu_baseline:
         host = types.SimpleNamespace(score_users=m.score_users)
         users = np.flatnonzero(np.diff(csr.indptr) > 0)
         sel = np.isin(data.test_u, users[:1000])
@@ -761,11 +812,13 @@ def main():
     ti = torch.from_numpy(train_i).to(dev)
     # per-batch plans: the epoch order is fixed for the whole fit (implicit.py:262), so
     # they are built once per fit, before timing (like the reference's own data
-    # preparation), for EVERY batch of the epoch in one launch (rg_mf_plans_build); the
-    # cost is measured (second build, warm) and reported beside the step
+    # preparation), for EVERY batch of the epoch in one launch (rg_mf_plans_build); with
+    # --full the cost is measured (a small build first, so the timed one is warm) and
+    # reported beside the step
     pstride = batch_lo[1] - batch_lo[0] if nbatches > 1 else B
     pkw = dict(users=tu) if own else {}
-    eng.make_plans(ti[:gb * 4], offset=batch_lo[0], stride=pstride, **({"users": tu[:gb * 4]} if own else {}))
+    if args.full:
+        eng.make_plans(ti[:gb * 4], offset=batch_lo[0], stride=pstride, **({"users": tu[:gb * 4]} if own else {}))
     torch.cuda.synchronize()
     tp0 = time.perf_counter()
     plans = eng.make_plans(ti, offset=batch_lo[0], stride=pstride, **pkw)[:nbatches]
@@ -783,7 +836,7 @@ def main():
 
     # step inputs (ids + plan pointers) built before timing; each call also hands the
     # NEXT step's input to the native stepper, which generates its words ahead
-    n_extra = 6          # untimed steps after the timed region (lazy-pass row counts)
+    n_extra = 6 if args.full else 0     # untimed steps after the timed region (lazy-pass row counts)
     inputs = [eng.step_input(*batch(s)[:2], gb, batch(s)[2]) for s in range(args.warmup + args.steps + n_extra + 2)]
 
     def step(s, ev=None):
@@ -840,8 +893,14 @@ def main():
     loss_last = float(eng.loss_out[0])
     if getattr(eng, "pipelined", False) and eng.pipe_error():
         raise RuntimeError("pipelined MF step: a pair workgroup's bounded wait ran out (results invalid)")
+    if args.dump_outputs:
+        # the tables after the last timed step (the flush above brought every row up to date)
+        arrays = dict(zip(("user_w", "item_w", "user_b", "item_b"), eng.params()))
+        arrays["loss"] = eng.loss_out[:1]
+        dump_outputs(args.dump_outputs, arrays, rank, world if emu is None else 1)
+    lazy = eng.lazy_rows(enable=False) is not None
     lazy_rows = None
-    if eng.lazy_rows(enable=True) is not None:
+    if args.full and eng.lazy_rows(enable=True) is not None:
         # untimed: user rows the lazy pass processes per step (the counter is contended, so it
         # runs only here), over steps that continue the timed sequence
         base = args.warmup + args.steps
@@ -877,10 +936,11 @@ def main():
                                                          " replicated (reduce-scatter + all-gather, reference-exact)"
                                                          if gs else "" if world == 1 else
                                                          " user-sharded (opt-in, not reference sampling)")},
-               "plan_build_us_per_batch": plan_us, "plan_build_ms_per_epoch": plan_epoch_s * 1e3,
                "plan_build_note": f"item-sorted plans of all {nbatches} batches of an epoch in one HIP launch "
                                   "(rg_mf_plans_build), built once per fit (the reference shuffles once, "
                                   "implicit.py:262); not in the timed region"}
+        if args.full:
+            out["plan_build_us_per_batch"], out["plan_build_ms_per_epoch"] = plan_us, plan_epoch_s * 1e3
         if rccl is not None:
             out["rccl"] = rccl
         step_bytes = gather + ids + adam
@@ -900,7 +960,8 @@ def main():
                         "gradient or the next step reads it, its skipped cold updates applied in order on the "
                         "way; bit-identical to the eager dense pass (tests/test_lazy_gpu.py); the timed region "
                         "ends with the flush that brings every row up to date"}
-        if any(ev is not None for ev in evs):
+        # the lazy pass's roofline counts the rows it processed: only known after --full's extra steps
+        if any(ev is not None for ev in evs) and (lazy_rows is not None or not lazy):
             from recommendation_gans_amd import _lib
             ms = [_lib.elapsed_ms(a, b) for a, b in (ev for ev in evs if ev is not None)]
             avg = float(np.mean(ms)) * 1e-3
@@ -943,7 +1004,7 @@ def main():
             # PMC traffic (scripts/pmc_apply.sh: FETCH_SIZE / WRITE_SIZE passes) of THIS build only:
             # the profile is stamped with the library's hash, a profile of another build is refused
             pmc = os.path.join(ROOT, "profiles", "pmc_step.json" if fused else "pmc_back.json")
-            if world == 1 and not own and not gs and lazy_rows is None and os.path.exists(pmc):
+            if args.full and world == 1 and not own and not gs and lazy_rows is None and os.path.exists(pmc):
                 import hashlib
                 p = json.load(open(pmc))
                 sha = hashlib.sha256(open(os.environ.get("RG_LIB") or rg_build.LIB, "rb").read()).hexdigest()[:16]
@@ -953,14 +1014,14 @@ def main():
                 else:
                     out["roofline"]["traffic_source"] = (f"profiles/{os.path.basename(pmc)} is of another build "
                                                          f"(lib {p.get('lib_sha16')} vs {sha}): not used")
-        if out.get("roofline"):
+        if args.full and out.get("roofline"):
             # the box's achievable HBM rate (STREAM-style copy, after the timed region), reported
             # beside the 8 TB/s nominal peak
             bw = stream_copy_gbs(dev)
             out["roofline"]["stream_copy_GBs"] = bw
             out["roofline"]["frac_of_stream_copy"] = out["roofline"]["achieved"] / bw
         out["final_loss"] = loss_last
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(data, d, B, n, args.loss, args.cpu_baseline_seconds)
         print(json.dumps(out), flush=True)
     if world > 1 or solo_pg:
