@@ -833,6 +833,27 @@ int rg_neumf_apply(void *stream, const rg_ncf_model_t *model, rg_mf_work_t *work
                    const rg_opt_t *opt, int64_t row_begin, int64_t row_end);
 
 /* ------------------------------------------------------------------------------
+ * NCF / NeuMF inference (rg_ncf_score.hip): eval-mode scores (no dropout) of a block of
+ * users against every item -- mlp.py:30-41 / neuMF.py:34-55 over (users[r], item c) --
+ * into out [n_users][ld] (device, fp32, ld >= num_items; columns [num_items, ld) are not
+ * written).  The first layer is split into a per-item and a per-user half (a small
+ * launch into `workspace`), the pair kernel runs the narrow layers on the MFMA over
+ * tiles of RG_NCF_SCORE_ITEM_TILE items x groups of RG_NCF_SCORE_USER_GROUP users.
+ * The model is only read (its moment pointers may be null); users_dev [n_users] int64
+ * ids are trusted to be in range; workspace_dev holds rg_ncf_score_workspace_len floats,
+ *     (num_items + n_users) * dim + n_users * ((mf_dim + 3) & ~3),
+ * 16-byte aligned.  Deterministic (no atomics).  Non-zero status (rg_last_error) on a
+ * null pointer, ld < num_items, an unsupported dim, mf_dim outside
+ * [0, RG_NEUMF_MAX_MF_DIM] or n_users < 0 (the length then is -1); n_users == 0: RG_OK,
+ * no launch.
+ * ---------------------------------------------------------------------------- */
+#define RG_NCF_SCORE_ITEM_TILE 64
+#define RG_NCF_SCORE_USER_GROUP 64
+int64_t rg_ncf_score_workspace_len(const rg_ncf_model_t *model, int64_t n_users);
+int rg_ncf_score_users(void *stream, const rg_ncf_model_t *model, const int64_t *users_dev, int64_t n_users,
+                       float *workspace_dev, float *out_dev, int64_t ld);
+
+/* ------------------------------------------------------------------------------
  * Evaluation top-k (rg_eval.hip): the first k entries of argsort(-scores) per row, as
  * precision_recall_score / hit_ratio / map_at_k read them (spotlight/evaluation.py:
  * 108-213, 278-353).  scores [rows][ld] (device, fp32), out_idx [rows][k] (device,

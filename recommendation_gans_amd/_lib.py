@@ -16,6 +16,8 @@ LIB_PATH = os.path.join(_PKG, "librg_hip.so")
 RG_OK = 0
 RG_MF_LIST_CAP = 8
 RG_MF_MAX_NEG = 8
+RG_NCF_SCORE_ITEM_TILE = 64      # rg_ncf_score_users: items per tile, users per group
+RG_NCF_SCORE_USER_GROUP = 64
 RG_COMM_ID_BYTES = 128
 RG_MT_PAD = 1280
 
@@ -245,6 +247,9 @@ SIGNATURES = [
     ("rg_mf_stepper_tail_gen", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MTGen)]),
     ("rg_topk_rows", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                      ctypes.c_int32, ctypes.c_void_p]),
+    ("rg_ncf_score_workspace_len", ctypes.c_int64, [ctypes.POINTER(NCFModel), ctypes.c_int64]),
+    ("rg_ncf_score_users", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(NCFModel), ctypes.c_void_p, ctypes.c_int64,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
     ("rg_mt_window_host", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     ("rg_mt_window_to_cpython", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
     ("rg_mt_advance_host", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),

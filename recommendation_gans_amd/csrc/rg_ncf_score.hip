@@ -1,0 +1,346 @@
+// NCF / NeuMF inference: eval-mode scores (no dropout) of a block of users against EVERY item
+// (spotlight/dnn_models/mlp.py:30-41, neuMF.py:34-55), the score block the evaluation metrics
+// and predict(user) rank (spotlight/evaluation.py: _scored, _topk_hits).
+//
+// Items are contiguous and the first (widest) layer separates:
+//     W1 [u; i] + b1 = (W1[:, :E] u + b1) + W1[:, E:] i = Hu[u] + Hi[i],
+// one vector per user and one per item, neither depending on the pair.  Two launches:
+//
+//   halves   Hi [I][E] = item_w W1[:, E:]^T,  Hu [nu][E] = user_w[users] W1[:, :E]^T + b1 and, for
+//            NeuMF, Gu [nu][MP] = affine_w[8:] * mf_user_w[users] (MP = M rounded up to 4, zero
+//            padded), so the GMF term of the logit is the plain dot Gu[u] . mf_item_w[i].
+//   scores   grid (item tile of 64, group of 64 users), 4 waves; wave w owns the group's users
+//            [16 w, 16 w + 16).  A lane (g = lane / 16, j = lane % 16) keeps its slice of the
+//            tile's Hi rows in registers for every user (item 16 nb + j of block nb, features
+//            16 t + 4 g .. + 3: the MFMA's B / C layout, as ncfw::fwd of rg_ncf.hip), so per
+//            (user, 16 items) the first layer is an add and a LeakyReLU.  The narrow layers
+//            E -> E/2 -> .. -> 8 run on __builtin_amdgcn_mfma_f32_16x16x4f32 with the weights in
+//            LDS (row-major [out][in + 4], the 8-wide layer padded to 16 rows of zeros), each
+//            layer's C tiles being the next layer's B operand with no shuffle.  The output dot
+//            (8 wide; the whole tower for E = 8) is VALU: four products per lane and a sum over
+//            the four lane groups.  The wave collects the 16 users' logits in the C layout of a
+//            (16 users x 16 items) tile -- which is where the GMF product Gu . mf_item^T of the
+//            same 16 users lands as M / 4 more MFMAs (mf_item rows of the tile staged in LDS once)
+//            -- then adds the bias, takes the sigmoid once per pair (precise expf, sigmoidf_ref)
+//            and stores out[u][i]: 16 consecutive items (64 B) per user and lane group.
+//
+// fp32 throughout, the model is only read, every sum has a fixed order (no atomics): two calls
+// give the same bits.  Item tails and the last user group are masked; out's padding columns
+// [I, ld) are not written.
+#include <climits>
+#include <utility>
+
+#include "rg_common.h"
+
+namespace rg {
+namespace {
+
+typedef float v4f __attribute__((ext_vector_type(4)));
+
+constexpr int kTile = RG_NCF_SCORE_ITEM_TILE, NB = kTile / 16;
+constexpr int kWaves = 4, kThreads = 64 * kWaves, kGroup = 16 * kWaves;
+static_assert(kGroup == RG_NCF_SCORE_USER_GROUP && kTile % 16 == 0, "header constants");
+constexpr int kHalfRows = 64;     // rows of Hi / Hu per workgroup of the halves pass
+
+__host__ __device__ constexpr int pad4(int m) { return (m + 3) & ~3; }
+// row stride of the staged mf_item rows: MP + 2, so the 16 rows x 2 k-columns a 32-lane half reads
+// (ds_read_b32, 32 banks) fall on 32 distinct banks ((MP + 2) / 2 is odd)
+__host__ __device__ constexpr int im_stride(int mp) { return mp + 2; }
+
+// layer k maps H(k) = 2E >> k features to H(k + 1); k = 0 is the split layer, k = NH the output
+template <int E>
+struct Shape {
+    static constexpr int NH = E == 8 ? 1 : E == 16 ? 2 : E == 32 ? 3 : 4;
+    static constexpr int H(int k) { return (2 * E) >> k; }
+    static constexpr int w_off(int k) {       // flat parameter offset of layer k (W then b)
+        int o = 0;
+        for (int j = 0; j < k; ++j) o += H(j + 1) * H(j) + H(j + 1);
+        return o;
+    }
+    // LDS (floats): weights of the MFMA layers 1 .. NH - 1, their biases, the output row, Hu rows
+    static constexpr int tiles(int k) { return H(k) < 16 ? 1 : H(k) / 16; }   // 16-feature tiles of layer k's input
+    static constexpr int rows(int k) { return 16 * tiles(k + 1); }
+    static constexpr int S(int k) { return H(k) + 4; }
+    static constexpr int lw_off(int k) {
+        int o = 0;
+        for (int j = 1; j < k; ++j) o += rows(j) * S(j);
+        return o;
+    }
+    static constexpr int lb_off(int k) {
+        int o = lw_off(NH);
+        for (int j = 1; j < k; ++j) o += rows(j);
+        return o;
+    }
+    static constexpr int oWo = lb_off(NH), oHu = oWo + 16, oIm = oHu + kGroup * E;
+    static constexpr int lds_floats(int mp) { return oIm + (mp ? kTile * im_stride(mp) : 0); }
+};
+
+template <class F, int... I>
+__device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, I...>) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void static_for(F &&f) {
+    static_for_impl(f, std::make_integer_sequence<int, N>{});
+}
+
+__device__ __forceinline__ v4f mfma(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+
+__device__ __forceinline__ v4f lrelu(v4f z) {
+    v4f y;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) y[r] = z[r] > 0.0f ? z[r] : z[r] * 0.1f;
+    return y;
+}
+
+struct HalvesArgs {
+    const float *user_w, *item_w, *mlp, *mf_user_w;
+    const int64_t *users;
+    int64_t num_items, n_users;
+    int M, MP;
+    float *Hi, *Hu, *Gu;
+};
+
+// blocks [0, ceil(I / 64)): rows of Hi; the rest: rows of Hu (and Gu) of 64 users each.  Thread
+// (row r = tid / E, feature e = tid % E): one k-ordered fmaf chain per output.
+template <int E>
+__global__ __launch_bounds__(kThreads) void ncf_score_halves_kernel(HalvesArgs a) {
+    using S = Shape<E>;
+    __shared__ float sWt[E * E];          // [k][e]: this half of W1, transposed
+    __shared__ float sX[kHalfRows * (E + 1)];
+    const int tid = threadIdx.x;
+    const int64_t item_blocks = (a.num_items + kHalfRows - 1) / kHalfRows;
+    const bool item_side = blockIdx.x < item_blocks;
+    const int64_t r0 = (item_side ? (int64_t)blockIdx.x : (int64_t)blockIdx.x - item_blocks) * kHalfRows;
+    const int64_t nrows = item_side ? a.num_items : a.n_users;
+    const float *W1 = a.mlp + S::w_off(0), *b1 = W1 + E * 2 * E;
+    for (int idx = tid; idx < E * E; idx += kThreads) {
+        const int e = idx / E, k = idx % E;
+        sWt[k * E + e] = W1[e * 2 * E + (item_side ? E : 0) + k];
+    }
+    for (int idx = tid; idx < kHalfRows * E; idx += kThreads) {
+        const int r = idx / E, k = idx % E;
+        float x = 0.0f;
+        if (r0 + r < nrows) x = item_side ? a.item_w[(r0 + r) * E + k] : a.user_w[a.users[r0 + r] * E + k];
+        sX[r * (E + 1) + k] = x;
+    }
+    __syncthreads();
+    const int e = tid % E;
+    const float bias = item_side ? 0.0f : b1[e];
+    float *dst = item_side ? a.Hi : a.Hu;
+    for (int r = tid / E; r < kHalfRows && r0 + r < nrows; r += kThreads / E) {
+        float acc = bias;
+#pragma unroll 8
+        for (int k = 0; k < E; ++k) acc = fmaf(sX[r * (E + 1) + k], sWt[k * E + e], acc);
+        dst[(r0 + r) * E + e] = acc;
+    }
+    if (!item_side && a.M > 0) {
+        const float *aw = a.mlp + S::w_off(S::NH) + 8;     // affine_output's GMF columns
+        for (int idx = tid; idx < kHalfRows * a.MP; idx += kThreads) {
+            const int r = idx / a.MP, c = idx % a.MP;
+            if (r0 + r < nrows)
+                a.Gu[(r0 + r) * a.MP + c] = c < a.M ? aw[c] * a.mf_user_w[a.users[r0 + r] * a.M + c] : 0.0f;
+        }
+    }
+}
+
+struct ScoreArgs {
+    const float *mlp, *Hi, *Hu, *Gu, *mf_item_w;
+    int64_t num_items, n_users, ld;
+    int M, MP;
+    float *out;
+};
+
+// layers K .. NH - 1 on the MFMA, x = layer K's input in the T layout (tile t, block nb, register
+// r: feature 16 t + 4 g + r of item 16 nb + j); last = the 8 (padded 16) inputs of the output dot
+template <int E, int K>
+__device__ __forceinline__ void tower(const v4f (&x)[Shape<E>::tiles(K)][NB], v4f (&last)[NB], const float *lds, int g,
+                                      int m) {
+    using S = Shape<E>;
+    if constexpr (K == S::NH) {
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) last[nb] = x[0][nb];
+    } else {
+        constexpr int TI = S::tiles(K), TO = S::tiles(K + 1), St = S::S(K);
+        const float *W = lds + S::lw_off(K), *B = lds + S::lb_off(K);
+        v4f y[TO][NB];
+#pragma unroll
+        for (int t = 0; t < TO; ++t) {
+            const v4f b = *reinterpret_cast<const v4f *>(B + 16 * t + 4 * g);
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) y[t][nb] = b;
+        }
+#pragma unroll
+        for (int ti = 0; ti < TI; ++ti) {
+            v4f a[TO];
+#pragma unroll
+            for (int t = 0; t < TO; ++t) a[t] = *reinterpret_cast<const v4f *>(W + (16 * t + m) * St + 16 * ti + 4 * g);
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int t = 0; t < TO; ++t)
+#pragma unroll
+                    for (int nb = 0; nb < NB; ++nb) y[t][nb] = mfma(a[t][r], x[ti][nb][r], y[t][nb]);
+        }
+#pragma unroll
+        for (int t = 0; t < TO; ++t)
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) y[t][nb] = lrelu(y[t][nb]);
+        tower<E, K + 1>(y, last, lds, g, m);
+    }
+}
+
+template <int E>
+__global__ __launch_bounds__(kThreads, 2) void ncf_score_kernel(ScoreArgs a) {
+    using S = Shape<E>;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, j = lane & 15;
+    const int64_t i0 = (int64_t)blockIdx.x * kTile, u0 = (int64_t)blockIdx.y * kGroup;
+    const int SM = im_stride(a.MP);
+
+    // ---- stage: the MFMA layers' weights and biases (zero padded), the output row, the group's Hu
+    // rows, the tile's mf_item rows
+    static_for<S::NH - 1>([&](auto kc) {
+        constexpr int K = decltype(kc)::value + 1, in = S::H(K), out = S::H(K + 1), R = S::rows(K), St = S::S(K);
+        const float *Wg = a.mlp + S::w_off(K);
+        for (int idx = tid; idx < R * St; idx += kThreads) {
+            const int r = idx / St, c = idx % St;
+            lds[S::lw_off(K) + idx] = r < out && c < in ? Wg[r * in + c] : 0.0f;
+        }
+        for (int idx = tid; idx < R; idx += kThreads) lds[S::lb_off(K) + idx] = idx < out ? Wg[out * in + idx] : 0.0f;
+    });
+    if (tid < 16) lds[S::oWo + tid] = tid < 8 ? a.mlp[S::w_off(S::NH) + tid] : 0.0f;
+    for (int idx = tid; idx < kGroup * E; idx += kThreads) {
+        const int64_t u = u0 + idx / E;
+        lds[S::oHu + idx] = u < a.n_users ? a.Hu[u * E + idx % E] : 0.0f;
+    }
+    if (a.M > 0)
+        for (int idx = tid; idx < kTile * SM; idx += kThreads) {
+            const int r = idx / SM, c = idx % SM;
+            lds[S::oIm + idx] = i0 + r < a.num_items && c < a.M ? a.mf_item_w[(i0 + r) * a.M + c] : 0.0f;
+        }
+    const float bo = a.mlp[S::w_off(S::NH) + 8 + a.M];
+    __syncthreads();                       // the only barrier: a wave without users may leave now
+    const int64_t uw = u0 + wave * 16;     // this wave's first user
+    if (uw >= a.n_users) return;
+
+    // ---- this lane's slice of the tile's Hi rows (rows past I read row I - 1; masked at the store)
+    constexpr int T0 = S::tiles(1);
+    const int fcol = E >= 16 ? 4 * g : 4 * (g & 1);    // E = 8: lane groups 2, 3 repeat 0, 1 under zero weights
+    v4f hi[T0][NB];
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+        int64_t item = i0 + 16 * nb + j;
+        item = item < a.num_items ? item : a.num_items - 1;
+#pragma unroll
+        for (int t = 0; t < T0; ++t) hi[t][nb] = *reinterpret_cast<const v4f *>(a.Hi + item * E + 16 * t + fcol);
+    }
+    const v4f wo = *reinterpret_cast<const v4f *>(lds + S::oWo + 4 * g);
+
+    // ---- the tower, one user at a time; acc[nb][r] = logit of (user uw + 4 g + r, item 16 nb + j)
+    v4f acc[NB];
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) acc[nb] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 1
+    for (int uu = 0; uu < 16; ++uu) {
+        if (uw + uu >= a.n_users) break;               // wave-uniform
+        const float *hu = lds + S::oHu + (wave * 16 + uu) * E;
+        v4f x[T0][NB];
+#pragma unroll
+        for (int t = 0; t < T0; ++t) {
+            const v4f h = *reinterpret_cast<const v4f *>(hu + 16 * t + fcol);
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) x[t][nb] = lrelu(hi[t][nb] + h);
+        }
+        v4f last[NB];
+        tower<E, 1>(x, last, lds, g, j);
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) {
+            float p = fmaf(wo[3], last[nb][3], fmaf(wo[2], last[nb][2], fmaf(wo[1], last[nb][1], wo[0] * last[nb][0])));
+            p += __shfl_xor(p, 16);
+            p += __shfl_xor(p, 32);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[nb][r] = 4 * g + r == uu ? p : acc[nb][r];
+        }
+    }
+
+    // ---- NeuMF: + Gu (16 users x MP) . mf_item^T (MP x 16 items) per block, into the same C tiles
+    if (a.M > 0) {
+        int64_t um = uw + j;
+        um = um < a.n_users ? um : a.n_users - 1;
+        const float *gp = a.Gu + um * a.MP + g;
+        const float *ip = lds + S::oIm + j * SM + g;
+        for (int k = 0; k < a.MP; k += 4) {
+            const float av = gp[k];
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) acc[nb] = mfma(av, ip[16 * nb * SM + k], acc[nb]);
+        }
+    }
+
+    // ---- bias, sigmoid, store (64 B of consecutive items per user and lane group)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int64_t u = uw + 4 * g + r;
+        if (u >= a.n_users) continue;
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) {
+            const int64_t item = i0 + 16 * nb + j;
+            if (item < a.num_items) a.out[u * a.ld + item] = sigmoidf_ref(acc[nb][r] + bo);
+        }
+    }
+}
+
+int score_check_model(const rg_ncf_model_t *m, int64_t n_users, const char *who) {
+    const std::string w(who);
+    if (!m) return fail_arg(w + ": null model");
+    if (rg_ncf_mlp_len(m->dim) < 0) return fail_arg(w + ": dim must be 8, 16, 32 or 64");
+    if (m->mf_dim < 0 || m->mf_dim > RG_NEUMF_MAX_MF_DIM) return fail_arg(w + ": mf_dim out of range");
+    if (m->num_items < 1 || m->num_users < 1) return fail_arg(w + ": empty tables");
+    if (n_users < 0) return fail_arg(w + ": n_users < 0");
+    return RG_OK;
+}
+
+template <int E>
+int score_launch(hipStream_t s, const rg_ncf_model_t *m, const int64_t *users, int64_t n_users, float *ws, float *out,
+                 int64_t ld) {
+    const int MP = pad4(m->mf_dim);
+    float *Hi = ws, *Hu = Hi + m->num_items * E, *Gu = Hu + n_users * E;
+    const HalvesArgs h{m->user_w, m->item_w, m->mlp, m->mf_user_w, users, m->num_items, n_users, m->mf_dim, MP, Hi, Hu, Gu};
+    const int64_t hblocks = (m->num_items + kHalfRows - 1) / kHalfRows + (n_users + kHalfRows - 1) / kHalfRows;
+    hipLaunchKernelGGL((ncf_score_halves_kernel<E>), dim3((unsigned)hblocks), dim3(kThreads), 0, s, h);
+    const ScoreArgs a{m->mlp, Hi, Hu, Gu, m->mf_item_w, m->num_items, n_users, ld, m->mf_dim, MP, out};
+    const dim3 grid((unsigned)((m->num_items + kTile - 1) / kTile), (unsigned)((n_users + kGroup - 1) / kGroup));
+    hipLaunchKernelGGL((ncf_score_kernel<E>), grid, dim3(kThreads), Shape<E>::lds_floats(MP) * sizeof(float), s, a);
+    return check_launch("rg_ncf_score_users");
+}
+
+}  // namespace
+}  // namespace rg
+
+using namespace rg;
+
+extern "C" int64_t rg_ncf_score_workspace_len(const rg_ncf_model_t *m, int64_t n_users) {
+    if (score_check_model(m, n_users, "rg_ncf_score_workspace_len") != RG_OK) return -1;
+    return (m->num_items + n_users) * m->dim + n_users * pad4(m->mf_dim);
+}
+
+extern "C" int rg_ncf_score_users(void *stream, const rg_ncf_model_t *m, const int64_t *users_dev, int64_t n_users,
+                                  float *workspace_dev, float *out_dev, int64_t ld) {
+    const int rc = score_check_model(m, n_users, "rg_ncf_score_users");
+    if (rc != RG_OK) return rc;
+    if (!users_dev || !workspace_dev || !out_dev || !m->user_w || !m->item_w || !m->mlp ||
+        (m->mf_dim > 0 && (!m->mf_user_w || !m->mf_item_w)))
+        return fail_arg("rg_ncf_score_users: null argument");
+    if (ld < m->num_items) return fail_arg("rg_ncf_score_users: ld < num_items");
+    if ((uintptr_t)workspace_dev % 16) return fail_arg("rg_ncf_score_users: workspace must be 16-byte aligned");
+    if (n_users == 0) return RG_OK;
+    if ((n_users + kGroup - 1) / kGroup > 65535 || (m->num_items + kHalfRows - 1) / kHalfRows > INT_MAX / 2)
+        return fail_arg("rg_ncf_score_users: too many users or items for one launch");
+    const hipStream_t s = (hipStream_t)stream;
+    switch (m->dim) {
+        case 8: return score_launch<8>(s, m, users_dev, n_users, workspace_dev, out_dev, ld);
+        case 16: return score_launch<16>(s, m, users_dev, n_users, workspace_dev, out_dev, ld);
+        case 32: return score_launch<32>(s, m, users_dev, n_users, workspace_dev, out_dev, ld);
+        default: return score_launch<64>(s, m, users_dev, n_users, workspace_dev, out_dev, ld);
+    }
+}

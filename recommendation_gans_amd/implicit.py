@@ -328,6 +328,11 @@ class ImplicitFactorizationModel:
     # ------------------------------------------------------------------ inference
     def predict(self, user_ids, item_ids=None):
         self._check_input(user_ids, item_ids, allow_items_none=True)
+        if item_ids is None and self._kind != "mf" and np.ndim(user_ids) == 0:
+            # one user against every item: the all-item kernel with a block of one user
+            if int(user_ids) < 0:
+                raise ValueError("user id must be non-negative")
+            return self._engine.score_users(np.array([int(user_ids)], dtype=np.int64)).cpu().numpy().flatten()
         if item_ids is None:
             item_ids = np.arange(self._num_items, dtype=np.int64)
         if np.isscalar(user_ids):
@@ -351,13 +356,11 @@ class ImplicitFactorizationModel:
 
     def _device_scores(self, u):
         """(len(u), num_items) fp32 scores on the device: one GEMM of the tables (MF), or
-        the eval-mode MLP / NeuMF over the block x items pairs."""
+        the eval-mode MLP / NeuMF block of the fused all-item kernel (rg_ncf_score_users)."""
         if self._kind == "mf":
             U, I, ub, ib = self._tables()
             return torch.sigmoid(U[u] @ I.T + ub[u][:, None] + ib[None, :])
-        items = torch.arange(self._num_items, device=u.device)
-        s = self._engine.scores(u.repeat_interleave(self._num_items), items.repeat(len(u)))
-        return s.reshape(len(u), self._num_items).detach()
+        return self._engine.score_users(u)
 
     def score_users(self, users):
         """Scores of every item for a block of users, (len(users), num_items) float32 on

@@ -457,6 +457,28 @@ class NCFEngine:
             x = torch.cat([x, self.mf_w[0][users] * self.mf_w[1][items]], 1)
         return torch.sigmoid(x @ ps[-2].T + ps[-1]).reshape(-1)
 
+    def score_users(self, users):
+        """Eval-mode scores (no dropout) of ``users`` against every item, (len(users), I) float32
+        on the device: rg_ncf_score_users (the split first layer's halves into a cached
+        workspace, then the fused pair kernel).  The engine's parameters are read in place, so
+        this holds after a data-parallel fit too (every rank has the same replica)."""
+        users = torch.as_tensor(users).to(self.device, torch.int64).reshape(-1).contiguous()
+        n = int(users.numel())
+        out = torch.empty(n, self.I, dtype=torch.float32, device=self.device)
+        if n == 0:
+            return out
+        if int(users.min()) < 0 or int(users.max()) >= self.U:
+            raise ValueError("user ids outside the user table")
+        need = int(self.lib.rg_ncf_score_workspace_len(ctypes.byref(self._model), n))
+        if need < 0:
+            raise RuntimeError("rg_ncf_score_workspace_len: " + self.lib.rg_last_error().decode())
+        ws = getattr(self, "_score_ws", None)
+        if ws is None or ws.numel() < need:
+            ws = self._score_ws = torch.empty(need, dtype=torch.float32, device=self.device)
+        check(self.lib.rg_ncf_score_users(_lib.stream_handle(), ctypes.byref(self._model), ptr(users), n, ptr(ws),
+                                          ptr(out), self.I), "rg_ncf_score_users")
+        return out
+
     def mt_state(self):
         host = np.zeros(625, dtype=np.uint32)
         check(self.lib.rg_mf_stepper_sync_mt(self._stepper, host.ctypes.data_as(ctypes.c_void_p), 0),
