@@ -744,7 +744,20 @@ typedef struct rg_ncf_work {
     float *scores;                          /* [tiles * rows_per_tile] (scores phase) */
     float *dp;                              /* [tiles * rows_per_tile] (given-dp phase) */
     const uint8_t *mask_pos, *mask_neg;     /* recorded dropout masks [rows][rg_ncf_mask_units] or null */
-    uint64_t seed;                          /* dropout hash seed when no masks are given */
+    /* Dropout hash seed of this step when no masks are given.  The contract (restated in NumPy
+     * by tests/ncf_common.py and held to the kernels by tests/test_ncf_dropout_gpu.py), all
+     * arithmetic unsigned with wrap-around, G = 0x9E3779B97F4A7C15:
+     *   seed           = any value the caller passes, one per step; NCFEngine (ncf_engine.py) sets
+     *                    engine seed * G + t (mod 2^64), t = 1 on its first training step
+     *   key(row)       = hash32(seed ^ (negative ? 1 << 40 : 0) ^ (gj * G mod 2^64)), hash32 = the
+     *                    low 32 bits of murmur3's fmix64; gj = the positive's global column
+     *                    (col_offset + its column in the caller's order, not the plan's), or the
+     *                    negative's global draw index (q - 1) * global_cols + that column
+     *   keep(row, unit) = (fmix32(key + unit * 0x85EBCA6B mod 2^32) >> 7) & 1, unit indexing the
+     *                    concatenated hidden layers as the recorded masks' columns do
+     * A kept unit is scaled by 1 / (1 - 0.5) = 2.  Both phases of adaptive hinge and every tile
+     * layout draw the same bit for the same (step, example, unit). */
+    uint64_t seed;
     int32_t training;                       /* 0: eval (no dropout) */
     int32_t tile_rows;                      /* rg_ncf_rows_per_tile(dim, mf_dim): the layout of
                                                contrib / scores / dp (rg_ncf_pairs checks it) */

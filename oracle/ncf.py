@@ -9,7 +9,8 @@ reference's NCF training step:
   * losses on (N, 1) scores            spotlight/losses.py:20-172 (as oracle/mf.py)
   * autograd of the above              implicit.py:361 (linear / leaky_relu /
       dropout / sigmoid backward as ATen computes them, dense embedding grads)
-  * Adam over every parameter          spotlight/optimizers.py:10-16, implicit.py:363
+  * Adam (default) / SGD / RMSprop     spotlight/optimizers.py:4-22, implicit.py:363
+      over every parameter (``optimizer=``; omf.Optim handles all three, its sensitivity too)
   * NeuMF.__init__ / forward           spotlight/dnn_models/neuMF.py:7-55
       the same tower (no output Linear inside), GMF branch U_mf[u] * I_mf[i],
       affine_output over cat([tower, gmf]) -> Sigmoid
@@ -195,7 +196,8 @@ class NCFOracle:
     N_EMB = 2                     # embedding tables before the Linears in parameter order
 
     def __init__(self, tensors, names, pool_u, pool_i, mt_state, loss="pointwise", lr=1e-2, weight_decay=1e-5,
-                 n_neg=5, batch_size=256, betas=(0.5, 0.999), order_seed=None, kink_flip=None, kink_env=None):
+                 n_neg=5, batch_size=256, betas=(0.5, 0.999), order_seed=None, kink_flip=None, kink_env=None,
+                 optimizer="adam", eps=1e-8, alpha=0.99):
         self.P = MLPParams(tensors, names)
         # order_seed (pointwise, test infrastructure): run the step over the examples, the input
         # features and every hidden layer's units in seeded orders -- the same arithmetic summed
@@ -217,8 +219,10 @@ class NCFOracle:
         self.kink_noise, self.kink_count = None, []
         self.loss_kind = loss
         self.n, self.batch_size = n_neg, batch_size
-        self.opt_lr, self.opt_wd, self.opt_betas = lr, weight_decay, betas
-        self.opt = omf.Optim("adam", self.P.t, lr, weight_decay, betas=betas)
+        # optimizer: "adam", "sgd" or "rms" (spotlight/optimizers.py:4-22 through omf.Optim)
+        self.opt_kind, self.opt_lr, self.opt_wd, self.opt_betas = optimizer, lr, weight_decay, betas
+        self.opt_eps, self.opt_alpha = eps, alpha
+        self.opt = omf.Optim(optimizer, self.P.t, lr, weight_decay, betas=betas, eps=eps, alpha=alpha)
         self.pool_u = torch.as_tensor(pool_u).long()
         self.pool_i = torch.as_tensor(pool_i).long()
         self.state = mt_state
@@ -382,4 +386,5 @@ class NeuMFOracle(NCFOracle):
     def __init__(self, tensors, names, *a, **k):
         super().__init__(tensors, names, *a, **k)
         self.P = NeuMFParams(tensors, names)
-        self.opt = omf.Optim("adam", self.P.t, self.opt_lr, self.opt_wd, betas=self.opt_betas)
+        self.opt = omf.Optim(self.opt_kind, self.P.t, self.opt_lr, self.opt_wd, betas=self.opt_betas,
+                             eps=self.opt_eps, alpha=self.opt_alpha)

@@ -1,0 +1,147 @@
+"""The NCF / NeuMF training kernels (rg_ncf.hip: the wave kernel at E = 64, the tile kernel at
+E in {8, 16, 32}, with and without the GMF branch) beyond the Adam path the sibling files hold:
+the SGD and RMSprop tails (rg_mlp_update.h, rg_common.h) against oracle.mf.Optim, every loss at
+the tile kernel's other widths, batch sizes around the tile's column count, a partial last batch
+with the full n * batch_size draw (implicit.py:347-364), and the eval-mode loss of
+run_val_iteration (implicit.py:366-379) on the tile kernel and NeuMF.
+
+Every training case is the pattern of test_ncf_e64_kernel_losses_and_shapes (tests/ncf_common.py
+run_parity): two native steps with random 0/1 dropout masks given to both sides against the
+oracle in fp32 and fp64 from the same init -- MT state bit-equal, loss 1e-5 relative, every
+parameter by oracle.mf.tensor_parity with its defaults.
+
+The partial last batch (n_pos in {1, 219} of 256, every loss): pointwise and adaptive hinge are
+what the reference computes for it (means over the n_pos positives and over all n * batch_size
+negatives; the maximum over all of them).  bpr_loss is unreachable from the reference's loss
+selection, and its hinge raises on a partial batch with n_pos > 1 (negatives (n * batch_size, 1)
+against positives (n_pos, 1) do not broadcast), as it does on a full batch with n > 1.  For those
+two the engine is held to the build's documented pairing, negatives.view(n, batch_size)[:, :n_pos]
+against the positives with the mean over n * n_pos pairs (oracle.mf.loss_and_dp),
+which is what the MF path's partial-batch tests hold too.
+
+A known divergence, pinned here rather than hidden: at n_pos = 1 the reference's hinge does define
+a result -- the single positive (1, 1) broadcasts against all n * batch_size negatives
+(losses.py:121-130) and the mean runs over all of them.  The engine keeps the documented pairing
+there too (column 0's n negatives, mean over n), as for every other n_pos; the hinge n_pos = 1
+cases below hold it to that pairing, not to the reference's broadcast."""
+import numpy as np
+import pytest
+import torch
+
+from oracle import mf as omf
+from oracle import rng as orng
+from tests import ncf_common as nc
+
+pytestmark = pytest.mark.gpu
+
+LOSSES = ["pointwise", "bpr", "hinge", "adaptive_hinge"]
+
+# ---------------------------------------------------------------------------- optimizers
+# (E, M): the wave kernel, the tile kernel, NeuMF with the GMF rows inside the dX region
+# (M <= E); tables of 60 x 25 rows, so most rows overflow their lists.  Each optimizer meets a
+# pointwise and a pairwise loss on every kernel; the pairwise one and the plan vary.
+OPT_CASES = [  # E, M, loss, optimizer, n_neg, planned
+    (64, 0, "pointwise", "sgd", 5, True), (64, 0, "bpr", "sgd", 4, False),
+    (64, 0, "pointwise", "rms", 5, False), (64, 0, "adaptive_hinge", "rms", 4, True),
+    (16, 0, "pointwise", "sgd", 5, False), (16, 0, "hinge", "sgd", 4, True),
+    (16, 0, "pointwise", "rms", 5, True), (16, 0, "bpr", "rms", 4, False),
+    (8, 5, "pointwise", "sgd", 5, True), (8, 5, "adaptive_hinge", "sgd", 4, False),
+    (8, 5, "pointwise", "rms", 5, False), (8, 5, "bpr", "rms", 4, True),
+    (32, 20, "pointwise", "sgd", 5, False), (32, 20, "bpr", "sgd", 4, True),
+    (32, 20, "pointwise", "rms", 5, True), (32, 20, "hinge", "rms", 4, False),
+    (32, 0, "pointwise", "adam", 5, True)]
+
+
+@pytest.mark.parametrize("E,M,loss,optimizer,n,planned", OPT_CASES)
+def test_ncf_optimizers_vs_oracle(E, M, loss, optimizer, n, planned):
+    nc.run_parity(E, M, loss, optimizer, n, B=300, U=60, I=25, planned=planned, seed=E + M + n)
+
+
+@pytest.mark.parametrize("E,M,loss", [(64, 0, "pointwise"), (16, 0, "bpr"), (8, 5, "pointwise"), (32, 20, "hinge")])
+def test_ncf_sgd_weight_decay_term(E, M, loss):
+    """SGD at weight_decay = 0.05: at the 1e-5 of the other cases the decay moves a tensor by
+    lr * wd = 1e-7 of its norm per step, which tensor_parity cannot see
+    (tests/test_ncf_controls_cpu.py); at 0.05 a missing or misplaced term is rejected."""
+    nc.run_parity(E, M, loss, "sgd", 5, B=300, U=60, I=25, planned=M == 0, seed=E + M, weight_decay=0.05)
+
+
+# ---------------------------------------------------------------------------- tile kernel widths
+# M = 0 at E = 8 and E = 32, all four losses, n in {1, 3, 8} (16, 8 and 3 columns per tile),
+# with and without a plan
+TILE_CASES = [(8, "pointwise", 1, False), (8, "bpr", 3, True), (8, "hinge", 8, False), (8, "adaptive_hinge", 3, True),
+              (32, "pointwise", 8, True), (32, "bpr", 1, False), (32, "hinge", 3, True),
+              (32, "adaptive_hinge", 8, False), (32, "adaptive_hinge", 1, True)]
+
+
+@pytest.mark.parametrize("E,loss,n,planned", TILE_CASES)
+def test_ncf_tile_kernel_widths_and_losses(E, loss, n, planned):
+    nc.run_parity(E, 0, loss, "adam", n, B=500, U=300, I=200, planned=planned, seed=E + n)
+
+
+# ---------------------------------------------------------------------------- batch edges
+def _tc(n, E):
+    from recommendation_gans_amd import _lib
+    return int(_lib.load().rg_ncf_cols_per_tile(n, E, 0))
+
+
+BATCHES = {"1": lambda tc: 1, "tc-1": lambda tc: tc - 1, "tc+1": lambda tc: tc + 1, "3tc+2": lambda tc: 3 * tc + 2}
+
+
+@pytest.mark.parametrize("loss", ["pointwise", "bpr"])
+@pytest.mark.parametrize("size", list(BATCHES))
+@pytest.mark.parametrize("E", [64, 16])
+def test_ncf_batch_sizes_around_the_tile(E, size, loss):
+    """batch_size in {1, tc - 1, tc + 1, 3 tc + 2} at n = 5, tc = rg_ncf_cols_per_tile(5, E, 0): one
+    column, a tile one column short, one column into a second tile, a partial fourth tile."""
+    tc = _tc(5, E)
+    B = BATCHES[size](tc)
+    assert tc > 1 and B >= 1
+    nc.run_parity(E, 0, loss, "adam", 5, B=B, U=200, I=150, planned=size in ("tc-1", "3tc+2"), seed=E + B)
+
+
+@pytest.mark.parametrize("loss,n_pos,planned", [("pointwise", 1, False), ("pointwise", 219, True),
+                                                ("adaptive_hinge", 1, True), ("adaptive_hinge", 219, False),
+                                                ("bpr", 1, False), ("bpr", 219, True),
+                                                ("hinge", 1, True), ("hinge", 219, False)])
+@pytest.mark.parametrize("E", [64, 16])
+def test_ncf_partial_last_batch(E, loss, n_pos, planned):
+    """n_pos < batch_size = 256 with the full n * 256 draw, as the end of every epoch produces
+    (the oracle is built with batch_size=256 and handed the short positives): see the module
+    docstring for what each loss is held to."""
+    nc.run_parity(E, 0, loss, "adam", 5, B=256, U=400, I=300, planned=planned, seed=E + n_pos, n_pos=n_pos)
+
+
+# ---------------------------------------------------------------------------- validation loss
+@pytest.mark.parametrize("loss", LOSSES)
+@pytest.mark.parametrize("M", [0, 5, 50])
+@pytest.mark.parametrize("E", [8, 16, 32])
+def test_ncf_tile_and_neumf_validation_loss(E, M, loss):
+    """run_val_iteration through the tile kernel's loss-only phase (adaptive hinge: its scores
+    phase) with and without the GMF branch: two batches against a float64 eval-mode forward
+    (GMF product included) on the same draw, 1e-5 relative; MT state bit-equal to that draw."""
+    from recommendation_gans_amd.ncf_engine import NCFEngine
+    dev = torch.device("cuda:0")
+    U, I, B, n = 500, 400, 300, 5
+    t, _ = nc.make_params(U, I, E, M, seed=100 + E + M)
+    ne = 4 if M else 2
+    rs = np.random.RandomState(E * 3 + M)
+    pool_u, pool_i = rs.randint(0, U, 20000), rs.randint(0, I, 20000)
+    mt = orng.py_seed_state(9)
+    extra = dict(mf_user_w=t[2], mf_item_w=t[3]) if M else {}
+    e = NCFEngine(t[0], t[1], t[ne:], pool_u, pool_i, mt.copy(), loss=loss, optimizer="adam", lr=1e-2,
+                  weight_decay=1e-5, n_neg=n, batch_size=B, device=dev, **extra)
+    state = mt.copy()
+    worst = 0.0
+    for s in range(2):
+        pu = torch.from_numpy(rs.randint(0, U, B))
+        pi = torch.from_numpy(rs.randint(0, I, B))
+        got = float(e.val_loss(pu.to(dev), pi.to(dev))[0])
+        idx = torch.from_numpy(orng.py_choices_indices(state, len(pool_u), n * B)).long()
+        nu, ni = torch.as_tensor(pool_u).long()[idx], torch.as_tensor(pool_i).long()[idx]
+        ref, _, _ = omf.loss_and_dp(loss, nc.eval_forward64(t, E, M, pu, pi), nc.eval_forward64(t, E, M, nu, ni), n, B)
+        torch.cuda.synchronize()
+        ref = float(ref)
+        worst = max(worst, abs(got - ref) / abs(ref))
+        assert abs(got - ref) <= 1e-5 * abs(ref), (E, M, loss, s, got, ref)
+        assert (e.mt_state() == state).all(), f"MT state after validation batch {s}"
+    print(f"E={E} M={M} {loss} validation loss: max rel diff {worst:.3g}")
