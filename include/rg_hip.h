@@ -876,6 +876,34 @@ int rg_topk_rows(void *stream, const float *scores, int64_t rows, int64_t cols, 
                  int32_t *out_idx);
 
 /* ------------------------------------------------------------------------------
+ * Evaluation ranks (rg_eval.hip): where given items stand in each row's full ranking,
+ * as mrr_score reads it (spotlight/evaluation.py:13-60: scipy rankdata of -score with
+ * the train items at FLOAT_MAX, ties averaged).  scores [rows][ld] (device, fp32, only
+ * read; columns [cols, ld) are padding and never read).  Targets and exclusions are
+ * CSR lists over the rows (device): row r's targets are tgt_idx[tgt_ptr[r] ..
+ * tgt_ptr[r + 1]), its excluded columns exc_idx[exc_ptr[r] .. exc_ptr[r + 1]); exc_ptr
+ * and exc_idx both null: no exclusions.  The key of column j of a row is
+ *     -FLT_MAX if j is excluded, else -inf if the score is NaN, else the score,
+ * and for the target t stored at tgt_idx[e]
+ *     out_above[e] = #{j < cols : key(j) >  key(t)}
+ *     out_equal[e] = #{j < cols : key(j) == key(t)}    (>= 1: t itself)
+ * so the average-tie rank of t is out_above + (out_equal + 1) / 2.  A target may be
+ * excluded or listed more than once (each entry gets its own output); an exclusion list
+ * may hold an id more than once.  An id outside [0, cols) is never used as an index: such
+ * a target gets out_above = -1, out_equal = 0, such an exclusion is ignored.  The targets
+ * of a row are counted RG_RANK_CHUNK at a time, one pass over the row per chunk; a row's
+ * exclusions are a bitmap of cols bits in LDS, hence cols <= RG_RANK_MAX_COLS.
+ * Deterministic (integer counts).  Non-zero status (rg_last_error) on a null scores /
+ * tgt_* / out_*, only one of exc_ptr / exc_idx, cols < 1, ld < cols, cols above
+ * RG_RANK_MAX_COLS or rows < 0; rows == 0: RG_OK, no launch.
+ * ---------------------------------------------------------------------------- */
+#define RG_RANK_CHUNK 16
+#define RG_RANK_MAX_COLS 1048576
+int rg_rank_rows(void *stream, const float *scores, int64_t rows, int64_t cols, int64_t ld,
+                 const int64_t *tgt_ptr, const int32_t *tgt_idx, const int64_t *exc_ptr, const int32_t *exc_idx,
+                 int32_t *out_above, int32_t *out_equal);
+
+/* ------------------------------------------------------------------------------
  * Negative pool (rg_pool.cpp, host code): spotlight/sampling.py:46-70
  * get_negative_samples, continuing NumPy's legacy global MT19937 (mt_key[624], mt_pos
  * from np.random.get_state(), advanced in place).  users / items of n draws

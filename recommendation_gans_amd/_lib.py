@@ -18,6 +18,8 @@ RG_MF_LIST_CAP = 8
 RG_MF_MAX_NEG = 8
 RG_NCF_SCORE_ITEM_TILE = 64      # rg_ncf_score_users: items per tile, users per group
 RG_NCF_SCORE_USER_GROUP = 64
+RG_RANK_CHUNK = 16               # rg_rank_rows: targets counted per pass over a row
+RG_RANK_MAX_COLS = 1 << 20       # rg_rank_rows: the exclusion bitmap's columns (LDS)
 RG_COMM_ID_BYTES = 128
 RG_MT_PAD = 1280
 
@@ -247,6 +249,9 @@ SIGNATURES = [
     ("rg_mf_stepper_tail_gen", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MTGen)]),
     ("rg_topk_rows", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                      ctypes.c_int32, ctypes.c_void_p]),
+    ("rg_rank_rows", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_void_p, ctypes.c_void_p]),
     ("rg_ncf_score_workspace_len", ctypes.c_int64, [ctypes.POINTER(NCFModel), ctypes.c_int64]),
     ("rg_ncf_score_users", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(NCFModel), ctypes.c_void_p, ctypes.c_int64,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),

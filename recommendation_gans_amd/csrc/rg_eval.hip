@@ -9,6 +9,7 @@
 // leaves the order of equal scores unspecified; for distinct scores the ranking is
 // the reference's).  Only users x k ids leave the device instead of the users x items
 // score block.
+#include <cfloat>
 #include <climits>
 
 #include "rg_common.h"
@@ -77,6 +78,110 @@ __global__ __launch_bounds__(kTopkThreads) void topk_kernel(const float *__restr
     if (tid < k) out[(int64_t)blockIdx.x * k + tid] = si[tid];
 }
 
+// ---------------------------------------------------------------- rank of given items
+// mrr_score (spotlight/evaluation.py:13-60) ranks every item of a user (scipy rankdata of
+// -score, ties averaged, train items at FLOAT_MAX) and reads the ranks of the test items.
+// The average-tie rank of a target t is above(t) + (equal(t) + 1) / 2, above = the items
+// ranked strictly ahead of t, equal = the items tied with it (t included): two integer
+// counts per target, no sort.
+//
+// One workgroup per row.  The row's excluded ids are set in an LDS bitmap, one bit per
+// column (a duplicate id sets the same bit again; an id outside [0, cols) is skipped).
+// The targets are taken kRankChunk at a time: their keys are held in registers, every
+// thread walks its strided slice of the row once per chunk and counts, per target, the
+// keys above and equal; the counts are summed over the wave by shuffles and over the
+// waves through LDS.  The row is re-read from L2 for each further chunk (targets x cols
+// compares per row, small next to producing the scores).
+constexpr int kRankThreads = 256;
+constexpr int kRankWaves = kRankThreads / kWave;
+constexpr int kRankChunk = RG_RANK_CHUNK;
+
+// key of column c: excluded -> -FLT_MAX (the reference's FLOAT_MAX on -score), NaN -> -inf
+template <bool EXC>
+__device__ __forceinline__ float rank_key(float x, int c, const uint32_t *bits) {
+    if (x != x) x = -INFINITY;
+    if (EXC && ((bits[c >> 5] >> (c & 31)) & 1u)) x = -FLT_MAX;
+    return x;
+}
+
+template <bool EXC>
+__global__ __launch_bounds__(kRankThreads) void rank_kernel(const float *__restrict__ scores, int cols, int64_t ld,
+                                                            const int64_t *__restrict__ tgt_ptr,
+                                                            const int32_t *__restrict__ tgt_idx,
+                                                            const int64_t *__restrict__ exc_ptr,
+                                                            const int32_t *__restrict__ exc_idx,
+                                                            int32_t *__restrict__ out_above,
+                                                            int32_t *__restrict__ out_equal) {
+    extern __shared__ uint32_t bits[];               // EXC: [(cols + 31) / 32]
+    __shared__ float tkey[kRankChunk];
+    __shared__ int part[kRankWaves][2 * kRankChunk];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const int64_t r = blockIdx.x;
+    const int64_t t0 = tgt_ptr[r], t1 = tgt_ptr[r + 1];
+    if (t1 <= t0) return;                            // the whole workgroup: no barrier is skipped
+    const float *row = scores + r * ld;
+    if (EXC) {
+        for (int w = tid; w < (cols + 31) / 32; w += kRankThreads) bits[w] = 0u;
+        __syncthreads();
+        const int64_t e1 = exc_ptr[r + 1];
+        for (int64_t e = exc_ptr[r] + tid; e < e1; e += kRankThreads) {
+            const int id = exc_idx[e];
+            if (id >= 0 && id < cols) atomicOr(&bits[id >> 5], 1u << (id & 31));
+        }
+        __syncthreads();
+    }
+    for (int64_t c0 = t0; c0 < t1; c0 += kRankChunk) {
+        const int n = (int)(t1 - c0 < kRankChunk ? t1 - c0 : kRankChunk);
+        // target id of this thread's slot; an id outside [0, cols) is never used as an index
+        const int my = tid < n ? tgt_idx[c0 + tid] : -1;
+        const bool my_ok = my >= 0 && my < cols;
+        if (tid < kRankChunk) tkey[tid] = my_ok ? rank_key<EXC>(row[my], my, bits) : NAN;   // NaN key: counts 0
+        __syncthreads();
+        float k[kRankChunk];
+        int above[kRankChunk], equal[kRankChunk];
+#pragma unroll
+        for (int j = 0; j < kRankChunk; ++j) { k[j] = tkey[j]; above[j] = 0; equal[j] = 0; }
+#pragma unroll 4
+        for (int c = tid; c < cols; c += kRankThreads) {
+            const float x = rank_key<EXC>(row[c], c, bits);
+#pragma unroll
+            for (int j = 0; j < kRankChunk; ++j) {
+                above[j] += x > k[j] ? 1 : 0;
+                equal[j] += x == k[j] ? 1 : 0;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kRankChunk; ++j) {
+            int a = above[j], q = equal[j];
+            for (int o = kWave / 2; o; o >>= 1) { a += __shfl_xor(a, o); q += __shfl_xor(q, o); }
+            if (lane == 0) { part[wave][j] = a; part[wave][kRankChunk + j] = q; }
+        }
+        __syncthreads();
+        if (tid < n) {
+            int a = 0, q = 0;
+            for (int w = 0; w < kRankWaves; ++w) { a += part[w][tid]; q += part[w][kRankChunk + tid]; }
+            out_above[c0 + tid] = my_ok ? a : -1;
+            out_equal[c0 + tid] = my_ok ? q : 0;
+        }
+    }
+}
+
+template <bool EXC>
+int rank_launch(hipStream_t s, const float *scores, int64_t rows, int cols, int64_t ld, const int64_t *tgt_ptr,
+                const int32_t *tgt_idx, const int64_t *exc_ptr, const int32_t *exc_idx, int32_t *out_above,
+                int32_t *out_equal) {
+    const size_t lds = EXC ? (size_t)((cols + 31) / 32) * sizeof(uint32_t) : 0;
+    if (EXC) {
+        static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void *>(rank_kernel<EXC>),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                     RG_RANK_MAX_COLS / 8) == hipSuccess;
+        if (!attr) return fail_arg("rg_rank_rows: cannot reserve LDS");
+    }
+    hipLaunchKernelGGL((rank_kernel<EXC>), dim3((unsigned)rows), dim3(kRankThreads), lds, s, scores, cols, ld, tgt_ptr,
+                       tgt_idx, exc_ptr, exc_idx, out_above, out_equal);
+    return check_launch("rg_rank_rows");
+}
+
 }  // namespace
 }  // namespace rg
 
@@ -99,4 +204,23 @@ extern "C" int rg_topk_rows(void *stream, const float *scores, int64_t rows, int
     else
         hipLaunchKernelGGL((topk_kernel<32>), grid, block, 0, s, scores, cols, ld, k, out_idx);
     return check_launch("rg_topk_rows");
+}
+
+extern "C" int rg_rank_rows(void *stream, const float *scores, int64_t rows, int64_t cols, int64_t ld,
+                            const int64_t *tgt_ptr, const int32_t *tgt_idx, const int64_t *exc_ptr,
+                            const int32_t *exc_idx, int32_t *out_above, int32_t *out_equal) {
+    if (!scores || !tgt_ptr || !tgt_idx || !out_above || !out_equal) return fail_arg("rg_rank_rows: null argument");
+    if ((exc_ptr == nullptr) != (exc_idx == nullptr))
+        return fail_arg("rg_rank_rows: exc_ptr and exc_idx must both be given or both be null");
+    if (rows < 0 || cols < 1 || ld < cols) return fail_arg("rg_rank_rows: bad shape");
+    if (cols > INT_MAX) return fail_arg("rg_rank_rows: cols must fit int32");
+    if (cols > RG_RANK_MAX_COLS)
+        return fail_arg("rg_rank_rows: cols above RG_RANK_MAX_COLS (" + std::to_string(RG_RANK_MAX_COLS) + ")");
+    if (rows == 0) return RG_OK;
+    if (rows > INT_MAX) return fail_arg("rg_rank_rows: too many rows for one launch");
+    const hipStream_t s = (hipStream_t)stream;
+    if (exc_ptr)
+        return rank_launch<true>(s, scores, rows, (int)cols, ld, tgt_ptr, tgt_idx, exc_ptr, exc_idx, out_above,
+                                 out_equal);
+    return rank_launch<false>(s, scores, rows, (int)cols, ld, tgt_ptr, tgt_idx, nullptr, nullptr, out_above, out_equal);
 }

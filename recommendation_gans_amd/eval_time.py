@@ -16,6 +16,14 @@ kernel path's algorithmic flops and bytes against the fp32 MFMA and HBM peaks.  
 also times the kernel path alone on a block of N users: the pairwise path is not run there, its
 concatenated input alone is N x items x 2E floats (56 GB at 4096 x 26,744 x 128).  One JSON line
 per model on stdout.
+
+    python -m recommendation_gans_amd.eval_time --metric mrr [--test-users 4096] [--reps 20]
+
+times ``evaluation.mrr_score`` instead, for an MF (d = 64) and an NCF (E = 64) model at 138,493
+users x ``--items`` items: ``--test-users`` test users of about 20 test items each, 100 train
+items each excluded.  The device path (``rank_users`` -> rg_rank_rows) and the host path (the
+score block copied to the host, scipy rankdata per user; one repetition) run on the same model
+object, wall time around calls that end on the host; the two results are compared.
 """
 import argparse
 import json
@@ -70,13 +78,115 @@ def timed(fn, reps):
     return [a.elapsed_time(b) for a, b in ev]
 
 
+class _HostOnly:
+    """The model's score block without its device ranking: mrr_score then takes the host path."""
+
+    def __init__(self, m):
+        self.score_users = m.score_users
+
+
+def mrr_data(U, I, n_test, seed=3, test_mean=20, train_per_user=100):
+    """``n_test`` random test users with about ``test_mean`` test items each (at least one) and
+    ``train_per_user`` train interactions each (the exclusions)."""
+    from .spotlight.interactions import Interactions
+    rs = np.random.RandomState(seed)
+    users = rs.choice(U, n_test, replace=False)
+    n_t = np.maximum(rs.poisson(test_mean, n_test), 1)
+    tu = np.repeat(users, n_t)
+    test = Interactions(tu.astype(np.int32), rs.randint(0, I, len(tu)).astype(np.int32), num_users=U, num_items=I)
+    ru = np.repeat(users, train_per_user)
+    train = Interactions(ru.astype(np.int32), rs.randint(0, I, len(ru)).astype(np.int32), num_users=U, num_items=I)
+    return test, train
+
+
+def mrr_model(kind, U, I, train):
+    """An initialised (untrained) ImplicitFactorizationModel: MF d = 64 or the NCF MLP E = 64."""
+    from .implicit import ImplicitFactorizationModel
+    from .spotlight.dnn_models.mlp import MLP
+    from .spotlight.factorization.representations import BilinearNet
+    torch.manual_seed(0)
+    if kind == "mf_d64":
+        net = BilinearNet(U, I, 64)
+        with torch.no_grad():                  # spread the scores (the default init leaves them all near 0.5)
+            net.user_embeddings.weight.normal_(0, 0.3)
+            net.item_embeddings.weight.normal_(0, 0.3)
+            net.item_biases.weight.normal_()
+    else:
+        net = MLP(layers=tower(64), num_users=U, num_items=I, embedding_dim=64)
+    model = ImplicitFactorizationModel(loss="pointwise", embedding_dim=64, n_iter=1, batch_size=256,
+                                       representation=net, random_state=np.random.RandomState(0),
+                                       neg_examples=[(0, 0), (1, 1)], num_negative_samples=3, use_cuda=True)
+    model._initialize(train)
+    return model
+
+
+def host_timed(fn, reps):
+    """Wall time (ms) of calls that end on the host, the device drained before and after."""
+    import time
+    ts, out = [], None
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return ts, out
+
+
+def main_mrr(args):
+    """``--metric mrr``: evaluation.mrr_score of the same model object on the device path
+    (rank_users -> rg_rank_rows) and on the host path (score block to the host, scipy rankdata
+    per user; one repetition), 4,096 test users with train exclusions."""
+    import os
+    import tempfile
+    from .spotlight import evaluation
+    U, I = 138493, args.items
+    test, train = mrr_data(U, I, args.test_users)
+    out = []
+    cwd = os.getcwd()
+    with tempfile.TemporaryDirectory() as td:
+        os.chdir(td)                           # the model writes its experiment folder under the cwd
+        try:
+            for kind in ("mf_d64", "ncf_e64"):
+                model = mrr_model(kind, U, I, train)
+                evaluation.mrr_score(model, test, train)                         # warm-up
+                t_dev, got = host_timed(lambda: evaluation.mrr_score(model, test, train), args.reps)
+                t_host, ref = host_timed(lambda: evaluation.mrr_score(_HostOnly(model), test, train), 1)
+                # where the device path's time goes: the score block alone (device events), and
+                # rank_users as a whole (score block + CSR upload + rg_rank_rows + counts download)
+                tcsr, xcsr = test.tocsr(), train.tocsr()
+                ub = np.flatnonzero(np.diff(tcsr.indptr) > 0)
+                ud = torch.as_tensor(ub, device=model._engine.device)
+                t_block = [timed(lambda: model._device_scores(ud), 1)[0] for _ in range(args.reps)]
+                t_rank, _ = host_timed(lambda: model.rank_users(ub, tcsr, xcsr), args.reps)
+                r = {"metric": "mrr", "model": kind, "users": U, "items": I, "test_users": int(len(got)),
+                     "test_items": int(len(test)), "train_items": int(len(train)), "reps": args.reps,
+                     "device_ms": {"min": min(t_dev), "median": float(np.median(t_dev))},
+                     "score_block_ms": {"min": min(t_block), "median": float(np.median(t_block))},
+                     "rank_users_ms": {"min": min(t_rank), "median": float(np.median(t_rank))},
+                     "host_ms": t_host[0], "speedup_min": t_host[0] / min(t_dev),
+                     "speedup_median": float(t_host[0] / np.median(t_dev)),
+                     "max_rel_diff": float((np.abs(got - ref) / ref).max()), "mean_mrr": float(got.mean())}
+                print(json.dumps(r), flush=True)
+                out.append(r)
+                del model
+                torch.cuda.empty_cache()
+        finally:
+            os.chdir(cwd)
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--metric", choices=("scores", "mrr"), default="scores")
     ap.add_argument("--users", type=int, default=256)
     ap.add_argument("--items", type=int, default=26744)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--big", type=int, default=0)
+    ap.add_argument("--test-users", type=int, default=4096)
     args = ap.parse_args(argv)
+    if args.metric == "mrr":
+        return main_mrr(args)
     dev = torch.device("cuda:0")
     U, I, n = 138493, args.items, args.users
     out = []

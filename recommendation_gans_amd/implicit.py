@@ -48,6 +48,17 @@ _LOSS_MAP = {"pointwise": "pointwise", "hinge": "hinge", "bpr": "adaptive_hinge"
              "adaptive_hinge": "adaptive_hinge", "pairwise_bpr": "bpr"}
 
 
+def _csr_rows(csr, rows):
+    """The CSR slice of ``rows`` (in that order, each row's indices as stored): (indptr int64
+    [len(rows) + 1], indices int32)."""
+    lo = csr.indptr[rows].astype(np.int64)
+    n = csr.indptr[rows + 1].astype(np.int64) - lo
+    ptr = np.zeros(len(rows) + 1, dtype=np.int64)
+    np.cumsum(n, out=ptr[1:])
+    pos = np.arange(ptr[-1], dtype=np.int64) + np.repeat(lo - ptr[:-1], n)
+    return ptr, csr.indices[pos].astype(np.int32)
+
+
 class ImplicitFactorizationModel:
     def __init__(self, loss="pointwise", embedding_dim=32, n_iter=10, batch_size=256, l2=0.0,
                  experiment_name="Implicit_Feedback", learning_rate=1e-2, optimizer_func=None, use_cuda=False,
@@ -389,6 +400,37 @@ class ImplicitFactorizationModel:
         _lib.check(lib.rg_topk_rows(_lib.stream_handle(), _lib.ptr(s), len(ub), self._num_items, self._num_items,
                                     int(k), _lib.ptr(out)), "rg_topk_rows")
         return out.cpu().numpy().astype(np.int64)
+
+    def rank_users(self, users, targets_csr, exclude_csr=None):
+        """The rank of every item of ``targets_csr``'s rows in the full ranking of a block of
+        users (evaluation.py:13-60, mrr_score: scipy rankdata of -score, ties averaged), counted
+        on the device by rg_rank_rows; items of ``exclude_csr``'s rows rank last (the reference's
+        FLOAT_MAX).  Returns a float64 array on the host, one rank per target: the users in the
+        order given, each user's targets in the order of its row's ``indices``.  Only the two
+        CSR slices go up and two int32 counts per target come down; the score block is only
+        read."""
+        from . import _lib
+        dev = self._engine.device
+        ub = np.asarray(users, dtype=np.int64)
+        t_ptr, t_idx = _csr_rows(targets_csr, ub)
+        if not len(t_idx):
+            return np.zeros(0, dtype=np.float64)
+        s = self._device_scores(torch.as_tensor(ub, device=dev)).to(torch.float32).contiguous()
+        tp, ti = torch.as_tensor(t_ptr, device=dev), torch.as_tensor(t_idx, device=dev)
+        ep = ei = None
+        if exclude_csr is not None:
+            e_ptr, e_idx = _csr_rows(exclude_csr, ub)
+            if len(e_idx):
+                ep, ei = torch.as_tensor(e_ptr, device=dev), torch.as_tensor(e_idx, device=dev)
+        counts = torch.empty(2, len(t_idx), dtype=torch.int32, device=dev)
+        lib = _lib.load()
+        _lib.check(lib.rg_rank_rows(_lib.stream_handle(), _lib.ptr(s), len(ub), self._num_items, self._num_items,
+                                    _lib.ptr(tp), _lib.ptr(ti), _lib.ptr(ep), _lib.ptr(ei), _lib.ptr(counts[0]),
+                                    _lib.ptr(counts[1])), "rg_rank_rows")
+        above, equal = counts.cpu().numpy().astype(np.float64)
+        if (above < 0).any():
+            raise ValueError("rank_users: target item id outside [0, num_items)")
+        return above + (equal + 1.0) / 2.0
 
     def test(self, test_set, item_popularity, k=5, rmse_flag=False, precision_recall=False, map_recall=True):
         test_results = {"k": k}

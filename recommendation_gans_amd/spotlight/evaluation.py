@@ -7,7 +7,8 @@ block of users against every item come from one GEMM on the device
 (``model.score_users``) instead of one ``predict`` call per user; the metrics that read
 only the first k ranks (precision/recall@k, hit ratio, MAP@k) take them from the
 device top-k (``model.topk_users`` -> rg_topk_rows) when the model has one and
-k <= 32, so only users x k ids reach the host."""
+k <= 32, so only users x k ids reach the host; mrr_score takes the ranks of the test items
+from the device (``model.rank_users`` -> rg_rank_rows) when the model has it."""
 import numpy as np
 import scipy.stats as st
 
@@ -88,7 +89,25 @@ def mrr_score(model, test, train=None):
     -score with ties averaged (scipy rankdata), train items pushed to the end."""
     test_csr = test.tocsr()
     train_csr = train.tocsr() if train is not None else None
+    if hasattr(model, "rank_users"):
+        return _mrr_from_ranks(model, test_csr, train_csr)
     return np.array([(1.0 / st.rankdata(pred)[idx]).mean() for _, idx, pred in _scored(model, test_csr, train_csr)])
+
+
+def _mrr_from_ranks(model, test_csr, train_csr, block=4096):
+    """mrr_score's device path (model.rank_users -> rg_rank_rows): the same users in the same
+    order as _scored, the ranks of each block's test items counted on the device (above +
+    (equal + 1) / 2 is rankdata's average-tie rank), so only two counts per test item reach the
+    host instead of the users x items score block."""
+    n_t = np.diff(test_csr.indptr)
+    users = np.flatnonzero(n_t > 0)
+    out = np.empty(len(users), dtype=np.float64)
+    for s in range(0, len(users), block):
+        ub = users[s:s + block]
+        n = n_t[ub]
+        ranks = np.asarray(model.rank_users(ub, test_csr, train_csr), dtype=np.float64)
+        out[s:s + len(ub)] = np.add.reduceat(1.0 / ranks, np.cumsum(n) - n) / n
+    return out
 
 
 def sequence_mrr_score(model, test, exclude_preceding=False):

@@ -1,0 +1,344 @@
+"""Evaluation ranks on the GPU (rg_rank_rows through the C-ABI) against the host ranking
+the reference uses for mrr_score (spotlight/evaluation.py:13-60): scipy rankdata of -score
+with the excluded items at FLOAT_MAX, turned back into the two counts (above = min rank - 1,
+equal = max rank - min rank + 1).  The counts are integers and are compared for equality:
+continuous and tied scores, padded row strides, every kind of target and exclusion list,
+NaN / inf scores, ids outside the row, bad arguments; then mrr_score through the drop-in
+evaluation module for a model over a fixed score matrix and for real MF / NCF / NeuMF
+models."""
+import numpy as np
+import pytest
+import scipy.stats as st
+import torch
+
+from recommendation_gans_amd import _lib
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+CHUNK = _lib.RG_RANK_CHUNK
+FLOAT_MAX = np.finfo(np.float32).max
+PAD = 7.0            # padding columns: above every score drawn here, so reading one changes `above`
+
+
+def csr_of(lists):
+    ptr = np.zeros(len(lists) + 1, dtype=np.int64)
+    np.cumsum([len(x) for x in lists], out=ptr[1:])
+    idx = np.concatenate([np.asarray(x, dtype=np.int32) for x in lists]) if len(lists) else np.zeros(0, np.int32)
+    return ptr, idx.astype(np.int32)
+
+
+def dev_i(a):
+    """Device copy of an index array; an empty one still gets a non-null pointer."""
+    t = torch.empty(max(len(a), 1), dtype=torch.from_numpy(a).dtype, device=DEV)
+    t[:len(a)] = torch.from_numpy(a).to(DEV)
+    return t
+
+
+def device_rank(scores, tgt, exc=None, ld=None):
+    """scores (rows, cols) float32 numpy; tgt / exc: one list of ids per row (exc None: NULL
+    pointers).  Returns (above, equal) in CSR order; checks that the scores were only read."""
+    lib = _lib.load()
+    rows, cols = scores.shape
+    ld = cols if ld is None else ld
+    buf = torch.full((rows, ld), PAD, dtype=torch.float32, device=DEV)
+    buf[:, :cols] = torch.from_numpy(scores).to(DEV)
+    before = buf.clone()
+    tp, ti = csr_of(tgt)
+    tpd, tid = dev_i(tp), dev_i(ti)
+    epd = eid = None
+    if exc is not None:
+        ep, ei = csr_of(exc)
+        epd, eid = dev_i(ep), dev_i(ei)
+    out = torch.full((2, max(len(ti), 1)), -9, dtype=torch.int32, device=DEV)
+    _lib.check(lib.rg_rank_rows(_lib.stream_handle(), _lib.ptr(buf), rows, cols, ld, _lib.ptr(tpd), _lib.ptr(tid),
+                                _lib.ptr(epd), _lib.ptr(eid), _lib.ptr(out[0]), _lib.ptr(out[1])), "rg_rank_rows")
+    torch.cuda.synchronize()
+    assert torch.equal(buf.view(torch.int32), before.view(torch.int32)), "the score block was written"
+    o = out.cpu().numpy()
+    return o[0, :len(ti)], o[1, :len(ti)]
+
+
+def host_rank(scores, tgt, exc=None):
+    """The reference's ranking per row (rankdata of -score, exclusions at FLOAT_MAX, NaN scores as
+    -inf, the documented key rule), as counts; a target outside the row: (-1, 0)."""
+    above, equal = [], []
+    cols = scores.shape[1]
+    for r in range(scores.shape[0]):
+        s = scores[r].astype(np.float32).copy()
+        s[np.isnan(s)] = -np.inf
+        pred = -s
+        if exc is not None:
+            e = np.asarray(exc[r], dtype=np.int64)
+            pred[e[(e >= 0) & (e < cols)]] = FLOAT_MAX
+        lo, hi = st.rankdata(pred, method="min"), st.rankdata(pred, method="max")
+        avg = st.rankdata(pred)
+        for t in tgt[r]:
+            if 0 <= t < cols:
+                a, q = int(lo[t]) - 1, int(hi[t] - lo[t]) + 1
+                assert a + (q + 1) / 2 == avg[t]              # the identity the device path rests on
+            else:
+                a, q = -1, 0
+            above.append(a)
+            equal.append(q)
+    return np.array(above, dtype=np.int32), np.array(equal, dtype=np.int32)
+
+
+def check(scores, tgt, exc=None, ld=None):
+    ga, ge = device_rank(scores, tgt, exc, ld)
+    ra, re_ = host_rank(scores, tgt, exc)
+    assert ga.dtype == np.int32 and ge.dtype == np.int32
+    assert (ga == ra).all(), (np.flatnonzero(ga != ra)[:8], ga[ga != ra][:8], ra[ga != ra][:8])
+    assert (ge == re_).all(), (np.flatnonzero(ge != re_)[:8], ge[ge != re_][:8], re_[ge != re_][:8])
+    return ga, ge
+
+
+def draw_scores(rs, rows, cols, kind):
+    s = rs.rand(rows, cols).astype(np.float32)
+    return (s * 8).round().astype(np.float32) / 8 if kind == "eighths" else s
+
+
+def target_list(rs, cols, kind):
+    """The target counts of the issue: 0, 1, one more than the kernel's chunk, 600, duplicates."""
+    if kind == "dup":
+        a, b = rs.randint(0, cols, 2)
+        return [a, a, b, a, b]
+    n = {"none": 0, "one": 1, "chunk+1": CHUNK + 1, "600": 600}[kind]
+    return rs.randint(0, cols, n).tolist()
+
+
+TARGET_KINDS = ["one", "chunk+1", "none", "600", "dup"]
+SHAPES = [(1, 1, 1), (1, 40, 40), (3, 64, 64), (5, 257, 257), (64, 777, 800), (7, 20108, 20108), (4, 50000, 50000)]
+
+
+@pytest.mark.parametrize("exclude", ["null", "random"])
+@pytest.mark.parametrize("kind", ["continuous", "eighths"])
+@pytest.mark.parametrize("rows,cols,ld", SHAPES)
+def test_counts_match_rankdata(rows, cols, ld, kind, exclude):
+    rs = np.random.RandomState(rows * 31 + cols)
+    s = draw_scores(rs, rows, cols, kind)
+    tgt = [target_list(rs, cols, TARGET_KINDS[(r + rows) % 5]) for r in range(rows)]
+    exc = None
+    if exclude == "random":
+        exc = [rs.randint(0, cols, rs.randint(0, max(2, cols // 3))).tolist() for _ in range(rows)]
+    check(s, tgt, exc, ld)
+
+
+@pytest.mark.parametrize("exclude", ["null", "random"])
+@pytest.mark.parametrize("kind", ["continuous", "eighths"])
+def test_every_target_count(kind, exclude):
+    """One row per target count (0, 1, chunk + 1, 600, duplicates) in one launch, twice over so
+    that an empty row stands between non-empty ones."""
+    rs = np.random.RandomState(5)
+    rows, cols = 10, 257
+    s = draw_scores(rs, rows, cols, kind)
+    tgt = [target_list(rs, cols, TARGET_KINDS[r % 5]) for r in range(rows)]
+    exc = [rs.randint(0, cols, 40).tolist() for _ in range(rows)] if exclude == "random" else None
+    ga, ge = check(s, tgt, exc)
+    assert len(ga) == 2 * (1 + CHUNK + 1 + 0 + 600 + 5)
+    assert (ge >= 1).all()
+
+
+def test_all_equal_row():
+    rs = np.random.RandomState(6)
+    s = draw_scores(rs, 3, 1000, "eighths")
+    s[1] = 0.375
+    tgt = [rs.randint(0, 1000, 20).tolist() for _ in range(3)]
+    ga, ge = check(s, tgt)
+    assert (ga[20:40] == 0).all() and (ge[20:40] == 1000).all()
+
+
+@pytest.mark.parametrize("kind", ["continuous", "eighths"])
+def test_exclusion_lists(kind):
+    """Exclusions holding some of the row's targets, a duplicated id, every item of a row
+    (once, and with duplicates), and an empty list among non-empty ones."""
+    rs = np.random.RandomState(7)
+    rows, cols = 6, 300
+    s = draw_scores(rs, rows, cols, kind)
+    tgt = [rs.randint(0, cols, 25).tolist() for _ in range(rows)]
+    exc = [tgt[0][:10] + rs.randint(0, cols, 30).tolist(),          # some of the targets
+           [17, 4, 17, 17, 250, 4] + tgt[1][:2] * 2,                # duplicated ids
+           list(range(cols)),                                        # the whole row
+           [],                                                       # empty between non-empty ones
+           rs.randint(0, cols, 100).tolist(),
+           list(range(cols)) + list(range(0, cols, 2))]             # the whole row, with duplicates
+    ga, ge = check(s, tgt, exc)
+    assert (ga[50:75] == 0).all() and (ge[50:75] == cols).all()     # all excluded: one tie of every item
+    # an excluded target ties with the other excluded items behind every kept one
+    n_exc = len(set(exc[0]))
+    assert (ga[:10] == cols - n_exc).all() and (ge[:10] == n_exc).all()
+
+
+@pytest.mark.parametrize("exclude", [False, True])
+def test_nan_and_infinities(exclude):
+    """NaN counts as -inf (rg_topk_rows' rule): it ties with the -inf scores, behind the
+    excluded items' -FLT_MAX; +inf ranks first."""
+    rs = np.random.RandomState(8)
+    cols = 500
+    s = draw_scores(rs, 2, cols, "eighths")
+    s[0, [3, 77, 401]] = np.nan
+    s[0, [5, 78]] = np.inf
+    s[0, [9, 402, 499]] = -np.inf
+    tgt = [[3, 5, 9, 77, 78, 100, 402, 499, 250], rs.randint(0, cols, 10).tolist()]
+    exc = [[77, 78, 9, 20, 21], [1, 2, 3]] if exclude else None
+    ga, ge = check(s, tgt, exc)
+    if not exclude:
+        assert ge[0] == 6 and ga[0] == cols - 6          # NaN ties with the three -inf and two more NaN
+        assert ga[1] == 0 and ge[1] == 2                 # the two +inf
+
+
+def test_ids_outside_the_row_are_refused():
+    """A target of cols or -1 writes (-1, 0) and leaves the row's other outputs alone; an
+    exclusion of cols is ignored."""
+    rs = np.random.RandomState(9)
+    cols = 200
+    s = draw_scores(rs, 3, cols, "eighths")
+    tgt = [[3, cols, 8, -1, 150], [cols], rs.randint(0, cols, CHUNK + 3).tolist() + [-1]]
+    exc = [[5, cols, 8], [cols], [1, 2]]
+    ga, ge = check(s, tgt, exc)
+    assert (ga[[1, 3, 5]] == -1).all() and (ge[[1, 3, 5]] == 0).all() and ga[-1] == -1 and ge[-1] == 0
+    good = [[3, 8, 150], [], tgt[2][:-1]]
+    ra, re_ = host_rank(s, good, [[5, 8], [], [1, 2]])
+    keep = np.array([0, 2, 4] + list(range(6, 6 + CHUNK + 3)))
+    assert (ga[keep] == ra).all() and (ge[keep] == re_).all()
+    check(s, tgt, None)
+
+
+@pytest.mark.parametrize("cols", [262144, _lib.RG_RANK_MAX_COLS])
+def test_widest_rows(cols):
+    """Every accepted width works, the exclusion bitmap's limit included."""
+    rs = np.random.RandomState(10)
+    s = draw_scores(rs, 2, cols, "eighths")
+    tgt = [rs.randint(0, cols, CHUNK + 1).tolist() + [cols - 1, 0], [cols - 1]]
+    exc = [rs.randint(0, cols, 5000).tolist() + [cols - 1], [0, cols - 2]]
+    check(s, tgt, exc)
+
+
+def test_bad_arguments_fail_loudly():
+    lib = _lib.load()
+    s = torch.rand(4, 10, device=DEV)
+    tp, ti = dev_i(np.arange(5, dtype=np.int64)), dev_i(np.zeros(4, np.int32))
+    out = torch.empty(2, 4, dtype=torch.int32, device=DEV)
+    sh = _lib.stream_handle()
+
+    def call(cols=10, ld=10, rows=4, sc=s, tptr=tp, tidx=ti, ep=None, ei=None, oa=out[0], oe=out[1]):
+        return lib.rg_rank_rows(sh, _lib.ptr(sc), rows, cols, ld, _lib.ptr(tptr), _lib.ptr(tidx), _lib.ptr(ep),
+                                _lib.ptr(ei), _lib.ptr(oa), _lib.ptr(oe))
+
+    def refused(**kw):
+        rc = call(**kw)
+        return rc != 0 and len(lib.rg_last_error()) > 0
+
+    assert call() == 0
+    assert refused(ld=9)
+    assert refused(cols=0, ld=10)
+    assert refused(ep=tp)                               # exc_ptr without exc_idx
+    assert refused(ei=ti)
+    assert refused(sc=None) and refused(tptr=None) and refused(tidx=None) and refused(oa=None) and refused(oe=None)
+    assert refused(cols=2 ** 31, ld=2 ** 31)
+    assert refused(cols=_lib.RG_RANK_MAX_COLS + 1, ld=_lib.RG_RANK_MAX_COLS + 1)
+    assert b"RG_RANK_MAX_COLS" in lib.rg_last_error()
+    assert call(rows=0) == 0
+    torch.cuda.synchronize()
+
+
+# ---------------------------------------------------------------- through the evaluation module
+class _DeviceModel:
+    """A model over a fixed device score matrix with both paths."""
+
+    def __init__(self, scores):
+        self.s = scores.to(DEV)
+        self.calls = 0
+
+    def score_users(self, users):
+        return self.s[torch.as_tensor(np.asarray(users), device=DEV)].cpu().numpy()
+
+    def rank_users(self, users, targets_csr, exclude_csr=None):
+        self.calls += 1
+        rows = [lambda c, u=u: c.indices[c.indptr[u]:c.indptr[u + 1]] for u in users]
+        exc = None if exclude_csr is None else [f(exclude_csr) for f in rows]
+        a, q = device_rank(self.score_users(users), [f(targets_csr) for f in rows], exc)
+        return a + (q + 1.0) / 2.0
+
+
+class _HostOnly:
+    def __init__(self, m):
+        self.score_users = m.score_users
+
+
+def test_mrr_from_device_ranks_matches_host_ranking():
+    from recommendation_gans_amd.spotlight import evaluation
+    from recommendation_gans_amd.spotlight.interactions import Interactions
+    rs = np.random.RandomState(0)
+    U, I = 300, 2000
+    m = _DeviceModel(torch.rand(U, I, generator=torch.Generator().manual_seed(1)))
+    test = Interactions(rs.randint(0, U, 3000), rs.randint(0, I, 3000), num_users=U, num_items=I)
+    train = Interactions(rs.randint(0, U, 9000), rs.randint(0, I, 9000), num_users=U, num_items=I)
+    h = _HostOnly(m)
+    for tr in (None, train):
+        got = evaluation.mrr_score(m, test, tr)
+        np.testing.assert_allclose(got, evaluation.mrr_score(h, test, tr), rtol=1e-12, atol=0)
+    assert m.calls == 2
+
+
+def tower(E):
+    sizes = [2 * E]
+    while sizes[-1] > 8:
+        sizes.append(sizes[-1] // 2)
+    return sizes
+
+
+def make_model(kind, tmp_path, monkeypatch):
+    from recommendation_gans_amd.implicit import ImplicitFactorizationModel
+    from recommendation_gans_amd.spotlight.dnn_models.mlp import MLP
+    from recommendation_gans_amd.spotlight.dnn_models.neuMF import NeuMF
+    from recommendation_gans_amd.spotlight.factorization.representations import BilinearNet
+    from recommendation_gans_amd.spotlight.interactions import Interactions
+    monkeypatch.chdir(tmp_path)
+    U, I, E, M = 50, 300, 16, 5
+    torch.manual_seed(11)
+    if kind == "mf":
+        net = BilinearNet(U, I, E)
+        with torch.no_grad():                  # spread the scores: the default init leaves them all near 0.5
+            net.user_embeddings.weight.normal_()
+            net.item_embeddings.weight.normal_()
+            net.item_biases.weight.normal_()
+    elif kind == "ncf":
+        net = MLP(layers=tower(E), num_users=U, num_items=I, embedding_dim=E)
+    else:
+        net = NeuMF(tower(E), U, I, mf_embedding_dim=M, mlp_embedding_dim=E)
+    rs = np.random.RandomState(4)
+    train = Interactions(rs.randint(0, U, 600).astype(np.int32), rs.randint(0, I, 600).astype(np.int32),
+                         ratings=np.ones(600, np.float32), num_users=U, num_items=I)
+    test = Interactions(rs.randint(0, U - 3, 400).astype(np.int32), rs.randint(0, I, 400).astype(np.int32),
+                        ratings=np.ones(400, np.float32), num_users=U, num_items=I)
+    pool = list(zip(rs.randint(0, U, 500).tolist(), rs.randint(0, I, 500).tolist()))
+    model = ImplicitFactorizationModel(loss="pointwise", embedding_dim=E, n_iter=1, batch_size=64, representation=net,
+                                       random_state=np.random.RandomState(0), neg_examples=pool,
+                                       num_negative_samples=3, use_cuda=True)
+    model._initialize(train)
+    return model, train, test
+
+
+@pytest.mark.parametrize("kind", ["mf", "ncf", "neumf"])
+def test_model_rank_users(kind, tmp_path, monkeypatch):
+    """rank_users of a real model equals the ranks computed on the host from the model's own
+    score block of the same users (exactly), and mrr_score takes it."""
+    from recommendation_gans_amd.spotlight import evaluation
+    model, train, test = make_model(kind, tmp_path, monkeypatch)
+    users = np.array([7, 3, 49, 3, 0, 48, 12, 30])         # a repeat, and users 48 / 49 without test items
+    tcsr, xcsr = test.tocsr(), train.tocsr()
+    block = model.score_users(users)
+    row = lambda c, u: c.indices[c.indptr[u]:c.indptr[u + 1]]
+    tgt = [row(tcsr, u) for u in users]
+    for exc_csr in (None, xcsr):
+        exc = None if exc_csr is None else [row(exc_csr, u) for u in users]
+        a, q = host_rank(block, tgt, exc)
+        got = model.rank_users(users, tcsr, exc_csr)
+        assert got.dtype == np.float64 and got.shape == (sum(len(t) for t in tgt),)
+        assert (got == a + (q + 1.0) / 2.0).all()
+    assert model.rank_users(np.array([48, 49]), tcsr, xcsr).shape == (0,)
+    h = _HostOnly(model)
+    for tr in (None, train):
+        np.testing.assert_allclose(evaluation.mrr_score(model, test, tr), evaluation.mrr_score(h, test, tr),
+                                   rtol=1e-12, atol=0)
