@@ -904,6 +904,28 @@ int rg_rank_rows(void *stream, const float *scores, int64_t rows, int64_t cols, 
                  int32_t *out_above, int32_t *out_equal);
 
 /* ------------------------------------------------------------------------------
+ * Slate hits (rg_eval.hip): which of the first k items of each generated slate are among
+ * the row's held-out items, as precision_recall_score_slates reads it (spotlight/
+ * evaluation.py:355-382).  slates [rows][ld] (device, int32, only read; columns
+ * [slate_size, ld) are padding and never read), targets as a CSR over the rows (device):
+ * row r's targets are tgt_idx[tgt_ptr[r] .. tgt_ptr[r + 1]), in any order, repeats allowed.
+ * out_mask[r] has bit j (j < k) set iff
+ *     slates[r][j] occurs among row r's targets, and
+ *     no j' < j has slates[r][j'] == slates[r][j],
+ * so popcount(out_mask[r]) == |set(slates[r][:k]) & set(targets of r)|: a repeated slate
+ * item counts once.  The ids are only compared, never used as indices: a slate id that is
+ * not among the row's targets (the padding id, a negative id) sets no bit.  A row without
+ * targets gets 0; every row's word is written on every call.  One wave per row,
+ * RG_SLATE_HITS_ROWS_PER_BLOCK rows per workgroup.  Deterministic (integer compares).
+ * Non-zero status (rg_last_error) on a null slates / tgt_* / out_mask, rows < 0,
+ * slate_size < 1, ld < slate_size, k outside [1, min(32, slate_size)] or rows above
+ * INT_MAX * RG_SLATE_HITS_ROWS_PER_BLOCK; rows == 0: RG_OK, no launch.
+ * ---------------------------------------------------------------------------- */
+#define RG_SLATE_HITS_ROWS_PER_BLOCK 4
+int rg_slate_hits(void *stream, const int32_t *slates, int64_t rows, int32_t slate_size, int64_t ld, int32_t k,
+                  const int64_t *tgt_ptr, const int32_t *tgt_idx, uint32_t *out_mask);
+
+/* ------------------------------------------------------------------------------
  * Negative pool (rg_pool.cpp, host code): spotlight/sampling.py:46-70
  * get_negative_samples, continuing NumPy's legacy global MT19937 (mt_key[624], mt_pos
  * from np.random.get_state(), advanced in place).  users / items of n draws

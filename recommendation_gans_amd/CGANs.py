@@ -32,13 +32,27 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .gan_engine import GANBatch, GANEngine
+from .gan_engine import GANBatch, GANEngine, csr_to_device
 from .spotlight import optimizers as sp_optimizers
-from .spotlight.evaluation import precision_recall_score_slates, precision_recall_slates_atk
+from .spotlight.evaluation import (SLATE_HITS_MAX_K, precision_recall_score_slates, precision_recall_slates_atk,
+                                   slate_precision_recall)
 from .spotlight.torch_utils import minibatch
 from .utils.storage_utils import save_statistics
 
 logging.basicConfig(format="%(message)s", level=logging.INFO)
+
+# CGAN.test uploads the padded history matrix (users x the longest history, int32) in chunks of
+# whole batches of at most this many bytes (every row is as wide as the longest history, so at
+# ML-20M's user count a few thousand columns already make it gigabytes)
+HIST_UPLOAD_BYTES = 256 << 20
+
+
+def _row_counts(csr, rows):
+    """Targets per user for the first ``rows`` rows of a CSR (rows past its last: 0)."""
+    n = np.zeros(rows, dtype=np.int64)
+    m = min(rows, csr.shape[0])
+    n[:m] = np.diff(csr.indptr[:m + 1])
+    return n
 
 
 class CGAN:
@@ -202,34 +216,69 @@ class CGAN:
         self.save_readable_model(self.experiment_saved_models, self.G.state_dict())
         self.training = False
 
+    def _history_chunks(self, train_vec):
+        """Yields (first row, device int32 histories) over ``train_vec`` in chunks of whole
+        batches of at most HIST_UPLOAD_BYTES, each range-checked on the host before it goes up
+        (GANBatch's rule: ids in [0, num_items], num_items = padding)."""
+        h = train_vec.detach().cpu().numpy() if torch.is_tensor(train_vec) else np.asarray(train_vec)
+        if not len(h):
+            return
+        B = self._batch_size
+        per = max(1, HIST_UPLOAD_BYTES // (4 * h.shape[1] * B)) * B
+        for r0 in range(0, len(h), per):
+            c = h[r0:r0 + per].astype(np.int64)
+            if c.min() < 0 or c.max() > self.num_items:
+                raise ValueError("history ids must lie in [0, num_items] (num_items = padding)")
+            yield r0, torch.from_numpy(c.astype(np.int32)).to(self.device)
+
+    def _slate_marks(self, chunks, users, csr):
+        """One group of users (histories in ``chunks``, held-out items in the CSR ``csr``): the
+        device int32 hit masks of their generated slates (GANEngine.slate_hits), or, for a slate
+        wider than a mask word, the slates themselves."""
+        S, dev = self.slate_size, self.device
+        if S > SLATE_HITS_MAX_K:
+            out = torch.empty(users, S, dtype=torch.int32, device=dev)
+            for r0, hist in chunks:
+                out[r0:r0 + hist.shape[0]] = self.engine.generate_slates(hist)
+            return out
+        tp, ti = csr_to_device(csr, users, dev)
+        out = torch.empty(users, dtype=torch.int32, device=dev)
+        for r0, hist in chunks:
+            r1 = r0 + hist.shape[0]
+            self.engine.slate_hits(hist, tp[r0:r1 + 1], ti, S, out=out[r0:r1])
+        return out
+
     def test(self, train_vec, test, cold_start_users=None):
         """CGANs.py:507-561: precision / recall@slate_size of the eval-mode generator's
         slates against each user's held-out items; cold-start users condition on the
-        padding item only.  Writes test_results.json."""
+        padding item only.  Writes test_results.json.
+
+        The slates never leave the device: the histories go up once as int32, the held-out
+        items once as a CSR, rg_slate_hits marks each slate's hits, and one word per user
+        comes down in a single copy for both groups of users.  The noise is drawn as before
+        (one torch.rand per batch, in batch order), so a seed gives the same figures."""
         if self.engine is None:
             raise RuntimeError("call fit() first")
-        total = {"precision": [], "recall": []}
+        S = self.slate_size
         test = test.tocsr()
-        for n, user_batch in enumerate(minibatch(train_vec, batch_size=self._batch_size)):
-            z = torch.rand(user_batch.shape[0], self.z_dim, device=self.device)
-            slates = self.engine.generate(self._batch(user_batch), z=z).cpu().type(torch.int64)
-            r0 = n * self._batch_size
-            p, r = precision_recall_score_slates(slates, test[r0:r0 + user_batch.shape[0], :], k=self.slate_size)
-            total["precision"] += p
-            total["recall"] += r
+        groups = [(self._slate_marks(self._history_chunks(train_vec), len(train_vec), test), test)]
         if cold_start_users is not None and cold_start_users.shape[0] > 0:
-            cold = torch.empty((cold_start_users.shape[0], self.embedding_dim)).fill_(self.num_items)
+            cold = torch.full((cold_start_users.shape[0], self.embedding_dim), self.num_items, dtype=torch.int32,
+                              device=self.device)
             cold_csr = cold_start_users.tocsr()
-            for n, user_batch in enumerate(minibatch(cold, batch_size=self._batch_size)):
-                z = torch.rand(user_batch.shape[0], self.z_dim, device=self.device)
-                slates = self.engine.generate(self._batch(user_batch), z=z).cpu().type(torch.int64)
-                r0 = n * self._batch_size
-                p, r = precision_recall_score_slates(slates, cold_csr[r0:r0 + user_batch.shape[0], :],
-                                                     k=self.slate_size)
-                total["precision"] += p
-                total["recall"] += r
-        res = {"precision": float(np.mean(total["precision"])) if total["precision"] else float("nan"),
-               "recall": float(np.mean(total["recall"])) if total["recall"] else float("nan"),
+            groups.append((self._slate_marks([(0, cold)], cold.shape[0], cold_csr), cold_csr))
+        if S > SLATE_HITS_MAX_K:
+            precision, recall = [], []
+            for slates, csr in groups:
+                p, r = precision_recall_score_slates(slates.cpu().type(torch.int64), csr[:slates.shape[0], :], k=S)
+                precision += p
+                recall += r
+        else:
+            masks = torch.cat([m for m, _ in groups]).cpu().numpy()
+            n = np.concatenate([_row_counts(csr, len(m)) for m, csr in groups])
+            precision, recall = slate_precision_recall(masks, n, S)
+        res = {"precision": float(np.mean(precision)) if precision else float("nan"),
+               "recall": float(np.mean(recall)) if recall else float("nan"),
                "at": self.slate_size}
         with open(os.path.join(self.experiment_logs, "test_results.json"), "w") as fp:
             json.dump(res, fp)

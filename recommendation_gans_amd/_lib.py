@@ -20,6 +20,8 @@ RG_NCF_SCORE_ITEM_TILE = 64      # rg_ncf_score_users: items per tile, users per
 RG_NCF_SCORE_USER_GROUP = 64
 RG_RANK_CHUNK = 16               # rg_rank_rows: targets counted per pass over a row
 RG_RANK_MAX_COLS = 1 << 20       # rg_rank_rows: the exclusion bitmap's columns (LDS)
+RG_SLATE_HITS_ROWS_PER_BLOCK = 4  # rg_slate_hits: rows (waves) per workgroup
+RG_SLATE_HITS_MAX_K = 32         # rg_slate_hits: one mask bit per slate position
 RG_COMM_ID_BYTES = 128
 RG_MT_PAD = 1280
 
@@ -252,6 +254,8 @@ SIGNATURES = [
     ("rg_rank_rows", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                      ctypes.c_void_p, ctypes.c_void_p]),
+    ("rg_slate_hits", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
+                                      ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("rg_ncf_score_workspace_len", ctypes.c_int64, [ctypes.POINTER(NCFModel), ctypes.c_int64]),
     ("rg_ncf_score_users", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(NCFModel), ctypes.c_void_p, ctypes.c_int64,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),

@@ -182,6 +182,56 @@ int rank_launch(hipStream_t s, const float *scores, int64_t rows, int cols, int6
     return check_launch("rg_rank_rows");
 }
 
+// ---------------------------------------------------------------- slate hits
+// precision / recall of a generated slate (spotlight/evaluation.py:355-382) read one number
+// per user: |set(slate[:k]) & set(targets)|.  It is the popcount of a k-bit word: bit j is set
+// when slate position j holds one of the row's targets and no earlier position holds the same
+// item.
+//
+// One wave per row, kHitsRows rows per workgroup.  Lane j < k loads slate position j; the k
+// ids are then read into scalar registers (readlane with constant lane numbers).  The lanes
+// stride over the row's targets, each compares its target with the k ids and ORs the matches
+// into its own word; the words are OR-ed over the wave by shuffles.  Lane j also finds whether
+// an earlier position holds its id, and a ballot gives those positions as a mask.  No LDS,
+// atomics or barriers, so a wave whose row is past the end or has no targets leaves early.
+constexpr int kHitsThreads = 256;
+constexpr int kHitsRows = RG_SLATE_HITS_ROWS_PER_BLOCK;
+constexpr int kHitsMaxK = 32;
+static_assert(kHitsRows * kWave == kHitsThreads, "one wave per row");
+
+template <int K>
+__global__ __launch_bounds__(kHitsThreads) void slate_hits_kernel(const int32_t *__restrict__ slates, int64_t rows,
+                                                                  int64_t ld, int k,
+                                                                  const int64_t *__restrict__ tgt_ptr,
+                                                                  const int32_t *__restrict__ tgt_idx,
+                                                                  uint32_t *__restrict__ out_mask) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t r = (int64_t)blockIdx.x * kHitsRows + __builtin_amdgcn_readfirstlane((int)threadIdx.x / kWave);
+    if (r >= rows) return;
+    const int64_t t0 = tgt_ptr[r], t1 = tgt_ptr[r + 1];
+    if (t1 <= t0) {
+        if (lane == 0) out_mask[r] = 0u;
+        return;
+    }
+    // positions [k, K) read as 0: whatever they match is cleared by the k-bit mask at the end
+    const int sid = lane < k ? slates[r * ld + lane] : 0;
+    int s[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) s[j] = __builtin_amdgcn_readlane(sid, j);
+    uint32_t m = 0u;
+    for (int64_t e = t0 + lane; e < t1; e += kWave) {
+        const int t = tgt_idx[e];
+#pragma unroll
+        for (int j = 0; j < K; ++j) m |= (t == s[j] ? 1u : 0u) << j;
+    }
+    for (int o = kWave / 2; o; o >>= 1) m |= __shfl_xor(m, o);
+    bool dup = false;
+#pragma unroll
+    for (int j = 0; j < K; ++j) dup |= j < lane && s[j] == sid;
+    const uint32_t dups = (uint32_t)__ballot(dup);      // bit j: an earlier position holds position j's item
+    if (lane == 0) out_mask[r] = m & ~dups & (k >= 32 ? 0xffffffffu : (1u << k) - 1u);
+}
+
 }  // namespace
 }  // namespace rg
 
@@ -223,4 +273,23 @@ extern "C" int rg_rank_rows(void *stream, const float *scores, int64_t rows, int
         return rank_launch<true>(s, scores, rows, (int)cols, ld, tgt_ptr, tgt_idx, exc_ptr, exc_idx, out_above,
                                  out_equal);
     return rank_launch<false>(s, scores, rows, (int)cols, ld, tgt_ptr, tgt_idx, nullptr, nullptr, out_above, out_equal);
+}
+
+extern "C" int rg_slate_hits(void *stream, const int32_t *slates, int64_t rows, int32_t slate_size, int64_t ld,
+                             int32_t k, const int64_t *tgt_ptr, const int32_t *tgt_idx, uint32_t *out_mask) {
+    if (!slates || !tgt_ptr || !tgt_idx || !out_mask) return fail_arg("rg_slate_hits: null argument");
+    if (rows < 0 || slate_size < 1 || ld < slate_size) return fail_arg("rg_slate_hits: bad shape");
+    if (k < 1 || k > kHitsMaxK || k > slate_size)
+        return fail_arg("rg_slate_hits: k must be in [1, min(32, slate_size)]");
+    if (rows > (int64_t)INT_MAX * kHitsRows) return fail_arg("rg_slate_hits: too many rows for one launch");
+    if (rows == 0) return RG_OK;
+    const dim3 grid((unsigned)((rows + kHitsRows - 1) / kHitsRows)), block(kHitsThreads);
+    const hipStream_t s = (hipStream_t)stream;
+    if (k <= 8)
+        hipLaunchKernelGGL((slate_hits_kernel<8>), grid, block, 0, s, slates, rows, ld, k, tgt_ptr, tgt_idx, out_mask);
+    else if (k <= 16)
+        hipLaunchKernelGGL((slate_hits_kernel<16>), grid, block, 0, s, slates, rows, ld, k, tgt_ptr, tgt_idx, out_mask);
+    else
+        hipLaunchKernelGGL((slate_hits_kernel<32>), grid, block, 0, s, slates, rows, ld, k, tgt_ptr, tgt_idx, out_mask);
+    return check_launch("rg_slate_hits");
 }

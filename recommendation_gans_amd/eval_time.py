@@ -24,6 +24,16 @@ users x ``--items`` items: ``--test-users`` test users of about 20 test items ea
 items each excluded.  The device path (``rank_users`` -> rg_rank_rows) and the host path (the
 score block copied to the host, scipy rankdata per user; one repetition) run on the same model
 object, wall time around calls that end on the host; the two results are compared.
+
+    python -m recommendation_gans_amd.eval_time --metric slates [--users 136677] [--reps 5]
+
+times one whole ``CGAN.test`` of ``--users`` users for the generator ``bench.py --model gan`` builds
+(S = 5, H = 256, E = 5, Z = 100, the ML-20M item count, reference initialisation, batch 256):
+synthetic padded histories of ``--hist-len`` columns and about 20 held-out items per user.  The
+device path (``CGAN.test``: rg_gan_generate per batch, one rg_slate_hits launch, one download) and
+the host path it replaced (per batch a GANBatch, ``generate``, ``.cpu()`` and the per-user set
+loop, restated here) run in the same process on the same engine under the same torch seed, wall
+time around calls that end on the host; the two results must be equal.
 """
 import argparse
 import json
@@ -35,6 +45,7 @@ from .ncf_engine import NCFEngine
 
 PEAK_FP32_MFMA = 157.3e12      # flop/s (spec)
 PEAK_HBM = 8.0e12              # B/s (spec)
+ML20M_USERS = 136677           # synthetic.ML20M["num_users"]
 
 
 def tower(E):
@@ -176,17 +187,106 @@ def main_mrr(args):
     return out
 
 
+def slates_data(U, N, L, seed=4, test_mean=20):
+    """Padded histories (U, L) as the data provider's float matrix (each user 1 .. L items, padding
+    N) and a CSR of about ``test_mean`` held-out items per user (one user in 16 has none)."""
+    import scipy.sparse as sp
+    rs = np.random.RandomState(seed)
+    hist = rs.randint(0, N, (U, L)).astype(np.float32)
+    hist[np.arange(L)[None, :] >= rs.randint(1, L + 1, U)[:, None]] = N
+    n_t = np.maximum(rs.poisson(test_mean, U), 1)
+    n_t[::16] = 0
+    ptr = np.zeros(U + 1, dtype=np.int64)
+    np.cumsum(n_t, out=ptr[1:])
+    idx = rs.randint(0, N, ptr[-1]).astype(np.int32)
+    return torch.from_numpy(hist), sp.csr_matrix((np.ones(len(idx), np.float32), idx, ptr), shape=(U, N))
+
+
+def host_cgan_test(model, train_vec, test):
+    """CGAN.test's regular-user loop as it stood before the device path: per batch a GANBatch
+    (with the grouping only training needs), generate, a download, and the per-user set loop."""
+    from .gan_engine import GANBatch
+    from .spotlight.evaluation import precision_recall_score_slates
+    from .spotlight.torch_utils import minibatch
+    B, S = model._batch_size, model.slate_size
+    total = {"precision": [], "recall": []}
+    for n, user_batch in enumerate(minibatch(train_vec, batch_size=B)):
+        z = torch.rand(user_batch.shape[0], model.z_dim, device=model.device)
+        batch = GANBatch(user_batch.numpy().astype(np.int64), None, model.num_items, S, model.device)
+        slates = model.engine.generate(batch, z=z).cpu().type(torch.int64)
+        p, r = precision_recall_score_slates(slates, test[n * B:n * B + user_batch.shape[0], :], k=S)
+        total["precision"] += p
+        total["recall"] += r
+    return {"precision": float(np.mean(total["precision"])), "recall": float(np.mean(total["recall"])), "at": S}
+
+
+def main_slates(args):
+    """``--metric slates``: one CGAN.test of ``--users`` users on the device path and on the host
+    path it replaced, same engine, same seed."""
+    import os
+    import tempfile
+    from .CGANs import CGAN
+    from .spotlight.dnn_models.cGAN_models import discriminator, generator
+    from .synthetic import ML20M
+    U, N, S, H, E, Z, B, L = args.users, ML20M["num_items"], 5, 256, 5, 100, 256, args.hist_len
+    train_vec, test = slates_data(U, N, L)
+    cwd = os.getcwd()
+    with tempfile.TemporaryDirectory() as td:
+        os.chdir(td)                           # the model writes its experiment folder under the cwd
+        try:
+            torch.manual_seed(0)
+            G = generator(num_items=N, noise_dim=Z, embedding_dim=E, hidden_layer=[H // 2, H], output_dim=S)
+            D = discriminator(num_items=N, embedding_dim=E, hidden_layers=[2 * H, H, H // 2], input_dim=S)
+            model = CGAN(G=G, D=D, z_dim=Z, n_iter=1, batch_size=B, slate_size=S, embedding_dim=E, hidden_layer=H,
+                         experiment_name="eval_time", use_cuda=True, random_state=np.random.RandomState(0))
+            model.num_users, model.num_items = U, N
+            model._initialize()
+
+            def seeded(fn):
+                def run():
+                    torch.manual_seed(1)
+                    return fn()
+                return run
+
+            dev = seeded(lambda: model.test(train_vec, test))
+            host = seeded(lambda: host_cgan_test(model, train_vec, test))
+            dev(), host()                                                        # warm-up
+            host_reps = max(1, min(args.reps, 3))
+            t_dev, got = host_timed(dev, args.reps)
+            t_host, ref = host_timed(host, host_reps)
+        finally:
+            os.chdir(cwd)
+    if got != ref:
+        raise SystemExit(f"the two paths disagree: device {got}, host {ref}")
+    r = {"metric": "slates", "users": U, "items": N, "hist_len": L, "slate_size": S, "hidden": H, "emb": E, "z": Z,
+         "batch": B, "test_items": int(test.nnz), "reps": args.reps, "host_reps": host_reps,
+         "device_ms": {"min": min(t_dev), "median": float(np.median(t_dev))},
+         "host_ms": {"min": min(t_host), "median": float(np.median(t_host))},
+         "speedup_min": min(t_host) / min(t_dev), "speedup_median": float(np.median(t_host) / np.median(t_dev)),
+         "results_equal": True, "precision": got["precision"], "recall": got["recall"]}
+    print(json.dumps(r), flush=True)
+    return [r]
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--metric", choices=("scores", "mrr"), default="scores")
-    ap.add_argument("--users", type=int, default=256)
+    ap.add_argument("--metric", choices=("scores", "mrr", "slates"), default="scores")
+    ap.add_argument("--users", type=int, default=None)
+    ap.add_argument("--hist-len", type=int, default=128)
     ap.add_argument("--items", type=int, default=26744)
-    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--reps", type=int, default=None)
     ap.add_argument("--big", type=int, default=0)
     ap.add_argument("--test-users", type=int, default=4096)
     args = ap.parse_args(argv)
+    slates = args.metric == "slates"             # its own defaults: every ML-20M user, 5 repetitions
+    if args.users is None:
+        args.users = ML20M_USERS if slates else 256
+    if args.reps is None:
+        args.reps = 5 if slates else 20
     if args.metric == "mrr":
         return main_mrr(args)
+    if slates:
+        return main_slates(args)
     dev = torch.device("cuda:0")
     U, I, n = 138493, args.items, args.users
     out = []

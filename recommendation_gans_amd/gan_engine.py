@@ -28,6 +28,46 @@ def ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
+def csr_to_device(csr, rows, device):
+    """The first ``rows`` rows of a scipy CSR as rg_slate_hits' targets: (tgt_ptr int64
+    (rows + 1), tgt_idx int32) on ``device``; rows past the matrix's last are empty, and an
+    empty index list still gets a valid pointer."""
+    n = min(rows, csr.shape[0])
+    tp = np.full(rows + 1, csr.indptr[n], dtype=np.int64)
+    tp[:n + 1] = csr.indptr[:n + 1]
+    ti = np.ascontiguousarray(csr.indices[:tp[-1]], dtype=np.int32)
+    if not len(ti):
+        ti = np.zeros(1, np.int32)
+    return torch.from_numpy(tp).to(device), torch.from_numpy(ti).to(device)
+
+
+def slate_hits(slates, tgt_ptr, tgt_idx, k, out=None):
+    """rg_slate_hits on device tensors: ``slates`` int32 (rows, S) with unit column stride,
+    ``tgt_ptr`` int64 (rows + 1) / ``tgt_idx`` int32 the rows' CSR targets, 1 <= k <= min(32, S).
+    Returns the int32 (rows,) masks (written into ``out`` when given).  No host
+    synchronisation: the arguments' dtypes and shapes are checked, the ids are not."""
+    rows, S = slates.shape
+    if slates.dtype != torch.int32 or not slates.is_cuda or (S > 1 and slates.stride(1) != 1) or \
+            (rows > 1 and slates.stride(0) < S):
+        raise ValueError("slates must be a device int32 (rows, S) tensor with contiguous rows")
+    if tgt_ptr.dtype != torch.int64 or tgt_idx.dtype != torch.int32 or tgt_ptr.numel() != rows + 1 or \
+            not (tgt_ptr.is_contiguous() and tgt_idx.is_contiguous()) or \
+            tgt_ptr.device != slates.device or tgt_idx.device != slates.device:
+        raise ValueError("tgt_ptr must be int64 (rows + 1) and tgt_idx int32, contiguous, on the slates' device")
+    if out is None:
+        out = torch.empty(rows, dtype=torch.int32, device=slates.device)
+    elif out.dtype not in (torch.int32, torch.uint32) or out.shape != (rows,) or not out.is_contiguous() or \
+            out.device != slates.device:
+        raise ValueError("out must be a contiguous int32 / uint32 (rows,) tensor on the slates' device")
+    if rows == 0:
+        return out
+    ld = slates.stride(0) if rows > 1 else S
+    stream = ctypes.c_void_p(torch.cuda.current_stream(slates.device).cuda_stream)
+    check(_lib.load().rg_slate_hits(stream, ptr(slates), rows, S, ld, int(k), ptr(tgt_ptr), ptr(tgt_idx), ptr(out)),
+          "rg_slate_hits")
+    return out
+
+
 class GANBatch:
     """Device form of one minibatch: histories (B, L) padded with N, target slates (B, S),
     the history items grouped per item (embedding backward) and the real slates as
@@ -290,6 +330,40 @@ class GANEngine:
                                        ptr(z), ptr(sl)), "rg_gan_generate")
         self._keep = [z]
         return sl
+
+    def generate_slates(self, hist):
+        """The eval-mode generator's slates of every row of ``hist`` (device int32 (users, L),
+        ids in [0, N], N = padding; the caller has checked the range), as a device int32
+        (users, S) tensor: one ``torch.rand(rows, Z)`` and one rg_gan_generate per consecutive
+        block of at most ``batch_max`` rows, in order (the draws ``CGAN.test`` always made, so a
+        seed gives the same slates).  The batch descriptor carries only the rows, the history
+        width and a pointer into ``hist``: inference reads nothing else of a batch.  No host
+        synchronisation."""
+        if hist.dtype != torch.int32 or hist.dim() != 2 or hist.device != self.device or not hist.is_contiguous():
+            raise ValueError("hist must be a contiguous int32 (users, L) tensor on the engine's device")
+        users, L = hist.shape
+        sl = torch.empty(users, self.S, dtype=torch.float32, device=self.device)
+        model, stream = self._model(), self._stream()
+        b = _lib.GANBatch()
+        b.hist_len = L
+        for r0 in range(0, users, self.batch_max):
+            rows = min(self.batch_max, users - r0)
+            z = torch.rand(rows, self.Z, device=self.device)
+            b.rows = rows
+            b.hist = ctypes.c_void_p(hist.data_ptr() + r0 * L * 4)
+            check(self.lib.rg_gan_generate(stream, ctypes.byref(model), ptr(self.ws), ctypes.byref(b), ptr(z),
+                                           ctypes.c_void_p(sl.data_ptr() + r0 * self.S * 4)), "rg_gan_generate")
+        return sl.to(torch.int32)
+
+    def slate_hits(self, hist, tgt_ptr, tgt_idx, k, out=None):
+        """Generates a slate for every row of ``hist`` (``generate_slates``) and marks, with one
+        rg_slate_hits launch over all rows, which of each slate's first k items are among the
+        row's held-out items: ``tgt_ptr`` (device int64, users + 1) and ``tgt_idx`` (device
+        int32) are the users' CSR.  Returns the device int32 tensor of masks (``out`` when
+        given): bit j of a row's word is set iff slate position j is a target and holds the
+        item's first occurrence in the slate, so the word's popcount is
+        len(set(slate[:k]) & set(targets)).  No host synchronisation."""
+        return slate_hits(self.generate_slates(hist), tgt_ptr, tgt_idx, k, out=out)
 
     def workspace_view(self, which, shape):
         off = int(self.lib.rg_gan_workspace_offset(ctypes.byref(self.dims), which))

@@ -8,7 +8,8 @@ block of users against every item come from one GEMM on the device
 only the first k ranks (precision/recall@k, hit ratio, MAP@k) take them from the
 device top-k (``model.topk_users`` -> rg_topk_rows) when the model has one and
 k <= 32, so only users x k ids reach the host; mrr_score takes the ranks of the test items
-from the device (``model.rank_users`` -> rg_rank_rows) when the model has it."""
+from the device (``model.rank_users`` -> rg_rank_rows) when the model has it;
+precision_recall_score_slates counts a device slates tensor's hits on the device (rg_slate_hits)."""
 import numpy as np
 import scipy.stats as st
 
@@ -227,11 +228,56 @@ def evaluate_random(item_popularity, test, k=10):
     return np.mean(np.array(precision).squeeze()), np.mean(np.array(recall).squeeze())
 
 
+SLATE_HITS_MAX_K = 32
+
+
+def slate_precision_recall(masks, n_targets, k):
+    """The precision / recall lists of precision_recall_score_slates from the device's hit
+    masks (rg_slate_hits: bit j of a user's word = slate position j is a first occurrence and
+    one of the user's targets) and each user's number of targets: for the users with targets,
+    in order, hits / k and hits / len(targets) in float64, hits = the set bits below k, which is
+    _get_precision_recall's len(set(pred[:k]) & set(targets))."""
+    m = np.ascontiguousarray(masks).reshape(-1)
+    m = m.view(np.uint32) if m.dtype == np.int32 else m.astype(np.uint32)
+    n = np.asarray(n_targets, dtype=np.int64).reshape(-1)
+    if k < 32:
+        m = m & np.uint32((1 << int(k)) - 1)
+    hits = np.unpackbits(m.view(np.uint8)).reshape(-1, 32).sum(axis=1)
+    keep = n > 0
+    hits = hits[keep].astype(np.float64)
+    return (hits / float(k)).tolist(), (hits / n[keep].astype(np.float64)).tolist()
+
+
+def _score_slates_device(slates, test, k):
+    """precision_recall_score_slates for a slates tensor on a GPU: the hits of every row counted
+    by one rg_slate_hits launch, one download of one word per row."""
+    import torch
+    from ..gan_engine import csr_to_device, slate_hits
+    rows = test.shape[0]
+    if slates.shape[0] < rows:
+        raise IndexError(f"{rows} test rows but only {slates.shape[0]} slates")
+    s = slates[:rows]
+    if not s.dtype.is_floating_point and s.dtype != torch.int32:
+        # an id outside int32 cannot be a CSR index; -1 is none either
+        s = torch.where((s >= -2 ** 31) & (s < 2 ** 31), s, -1)
+    s = s.to(torch.int32).contiguous()
+    tp, ti = csr_to_device(test, rows, s.device)
+    masks = slate_hits(s, tp, ti, min(k, s.shape[1])).cpu().numpy()
+    return slate_precision_recall(masks, np.diff(test.indptr), k)
+
+
 def precision_recall_score_slates(slates, test, k=3):
     """spotlight/evaluation.py:355-382: precision / recall@k of each test user's
-    generated slate (row u of ``slates`` belongs to row u of the CSR ``test``)."""
+    generated slate (row u of ``slates`` belongs to row u of the CSR ``test``).  A slates
+    tensor on a GPU is counted there (rg_slate_hits) when k <= 32; CPU tensors and arrays
+    take the host loop."""
     ks = np.array([k]) if np.isscalar(k) else np.asarray(k)
     test = test.tocsr()
+    if getattr(slates, "is_cuda", False):
+        k0 = int(ks.reshape(-1)[0])                     # only the first k's figures are returned
+        if slates.dim() == 2 and 1 <= min(k0, slates.shape[1]) <= SLATE_HITS_MAX_K:
+            return _score_slates_device(slates, test, k0)
+        slates = slates.cpu()
     precision, recall = [], []
     for user_id in range(test.shape[0]):
         targets = test.indices[test.indptr[user_id]:test.indptr[user_id + 1]]
