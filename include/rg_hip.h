@@ -865,6 +865,24 @@ int rg_neumf_apply(void *stream, const rg_ncf_model_t *model, rg_mf_work_t *work
 int64_t rg_ncf_score_workspace_len(const rg_ncf_model_t *model, int64_t n_users);
 int rg_ncf_score_users(void *stream, const rg_ncf_model_t *model, const int64_t *users_dev, int64_t n_users,
                        float *workspace_dev, float *out_dev, int64_t ld);
+/* The same forward for arbitrary pairs: out_dev[p] (device, fp32) = the eval-mode score of
+ * (users_dev[p], items_dev[p]), p in [0, n); out_dev[n ..] is never written.  One launch, no
+ * workspace, no atomics: a workgroup (4 waves) stages every layer's weights in LDS once
+ * (row-major [out][in + 4], rows padded to 16 with zeros; 47,168 B at dim 64 with
+ * mf_dim 128) and walks tiles of RG_NCF_SCORE_PAIR_TILE pairs, a wave owning 32 of them
+ * as two MFMA column blocks.  Each lane loads its 16-byte slices of the pair's
+ * [user row | item row] straight into the MFMA's B layout, every layer 2 dim -> dim ->
+ * ... -> 8 (the first included) runs on v_mfma_f32_16x16x4_f32, the 8-wide output dot,
+ * the GMF term and the sigmoid stay in registers, one store per pair.  Every sum has a
+ * fixed order that does not depend on the pair's position: a pair's score is the same
+ * bits at any position, in any batch, on any call.  The model is only read (its moment
+ * pointers may be null); the int64 ids are trusted to be in range.  Non-zero status
+ * (rg_last_error) on a null model, table, mlp, users, items or out pointer, mf_dim > 0
+ * without the GMF tables, an unsupported dim, mf_dim outside [0, RG_NEUMF_MAX_MF_DIM],
+ * n < 0, or embedding tables that are not 16-byte aligned; n == 0: RG_OK, no launch. */
+#define RG_NCF_SCORE_PAIR_TILE 128
+int rg_ncf_score_pairs(void *stream, const rg_ncf_model_t *model, const int64_t *users_dev, const int64_t *items_dev,
+                       int64_t n, float *out_dev);
 
 /* ------------------------------------------------------------------------------
  * Evaluation top-k (rg_eval.hip): the first k entries of argsort(-scores) per row, as

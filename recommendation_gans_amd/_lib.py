@@ -18,6 +18,7 @@ RG_MF_LIST_CAP = 8
 RG_MF_MAX_NEG = 8
 RG_NCF_SCORE_ITEM_TILE = 64      # rg_ncf_score_users: items per tile, users per group
 RG_NCF_SCORE_USER_GROUP = 64
+RG_NCF_SCORE_PAIR_TILE = 128     # rg_ncf_score_pairs: pairs per tile (32 per wave)
 RG_RANK_CHUNK = 16               # rg_rank_rows: targets counted per pass over a row
 RG_RANK_MAX_COLS = 1 << 20       # rg_rank_rows: the exclusion bitmap's columns (LDS)
 RG_SLATE_HITS_ROWS_PER_BLOCK = 4  # rg_slate_hits: rows (waves) per workgroup
@@ -259,6 +260,8 @@ SIGNATURES = [
     ("rg_ncf_score_workspace_len", ctypes.c_int64, [ctypes.POINTER(NCFModel), ctypes.c_int64]),
     ("rg_ncf_score_users", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(NCFModel), ctypes.c_void_p, ctypes.c_int64,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
+    ("rg_ncf_score_pairs", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(NCFModel), ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_int64, ctypes.c_void_p]),
     ("rg_mt_window_host", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     ("rg_mt_window_to_cpython", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
     ("rg_mt_advance_host", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),

@@ -27,6 +27,9 @@
 // fp32 throughout, the model is only read, every sum has a fixed order (no atomics): two calls
 // give the same bits.  Item tails and the last user group are masked; out's padding columns
 // [I, ld) are not written.
+//
+// Arbitrary (user, item) pairs (predict(users, items)) cannot split the first layer; they have a
+// kernel of their own below (rg_ncf_score_pairs), which shares the tower and the LDS weight layout.
 #include <climits>
 #include <utility>
 
@@ -153,22 +156,23 @@ struct ScoreArgs {
 
 // layers K .. NH - 1 on the MFMA, x = layer K's input in the T layout (tile t, block nb, register
 // r: feature 16 t + 4 g + r of item 16 nb + j); last = the 8 (padded 16) inputs of the output dot
-template <int E, int K>
-__device__ __forceinline__ void tower(const v4f (&x)[Shape<E>::tiles(K)][NB], v4f (&last)[NB], const float *lds, int g,
+// (L: where the layers' weights and biases sit in LDS; N: 16-column blocks per wave)
+template <int E, int K, class L = Shape<E>, int N = NB>
+__device__ __forceinline__ void tower(const v4f (&x)[Shape<E>::tiles(K)][N], v4f (&last)[N], const float *lds, int g,
                                       int m) {
     using S = Shape<E>;
     if constexpr (K == S::NH) {
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) last[nb] = x[0][nb];
+        for (int nb = 0; nb < N; ++nb) last[nb] = x[0][nb];
     } else {
         constexpr int TI = S::tiles(K), TO = S::tiles(K + 1), St = S::S(K);
-        const float *W = lds + S::lw_off(K), *B = lds + S::lb_off(K);
-        v4f y[TO][NB];
+        const float *W = lds + L::lw_off(K), *B = lds + L::lb_off(K);
+        v4f y[TO][N];
 #pragma unroll
         for (int t = 0; t < TO; ++t) {
             const v4f b = *reinterpret_cast<const v4f *>(B + 16 * t + 4 * g);
 #pragma unroll
-            for (int nb = 0; nb < NB; ++nb) y[t][nb] = b;
+            for (int nb = 0; nb < N; ++nb) y[t][nb] = b;
         }
 #pragma unroll
         for (int ti = 0; ti < TI; ++ti) {
@@ -180,13 +184,13 @@ __device__ __forceinline__ void tower(const v4f (&x)[Shape<E>::tiles(K)][NB], v4
 #pragma unroll
                 for (int t = 0; t < TO; ++t)
 #pragma unroll
-                    for (int nb = 0; nb < NB; ++nb) y[t][nb] = mfma(a[t][r], x[ti][nb][r], y[t][nb]);
+                    for (int nb = 0; nb < N; ++nb) y[t][nb] = mfma(a[t][r], x[ti][nb][r], y[t][nb]);
         }
 #pragma unroll
         for (int t = 0; t < TO; ++t)
 #pragma unroll
-            for (int nb = 0; nb < NB; ++nb) y[t][nb] = lrelu(y[t][nb]);
-        tower<E, K + 1>(y, last, lds, g, m);
+            for (int nb = 0; nb < N; ++nb) y[t][nb] = lrelu(y[t][nb]);
+        tower<E, K + 1, L, N>(y, last, lds, g, m);
     }
 }
 
@@ -290,6 +294,134 @@ __global__ __launch_bounds__(kThreads, 2) void ncf_score_kernel(ScoreArgs a) {
     }
 }
 
+// ---------------------------------------------------------------- arbitrary (user, item) pairs
+// rg_ncf_score_pairs: nothing separates, so the first layer is a real 2E-wide product and runs on
+// the MFMA like the rest.  A workgroup stages EVERY layer's weights in LDS once (the layout of the
+// all-item kernel: row-major [out][in + 4], rows padded to 16 with zeros) and then walks tiles of
+// RG_NCF_SCORE_PAIR_TILE pairs, tile = blockIdx.x, + gridDim.x, ...; wave w owns pairs
+// [32 w, 32 w + 32) of a tile as two MFMA column blocks.  A lane (g, j) loads its slice of pair
+// 16 nb + j's input straight from the tables in the B layout: features 16 t + 4 g .. + 3 of
+// [user_w[u] | item_w[i]], one 16-byte load each, the four lane groups of a pair covering 64
+// consecutive bytes of a row -- no LDS round trip and no shuffle.  After the tower the lane holds
+// four products of the 8-wide output dot; NeuMF adds its share of the GMF term (columns c = g
+// mod 4 of affine_w[8 + c] * mf_user_w[u][c] * mf_item_w[i][c], c ascending); two shuffles sum
+// the four lane groups, then bias, sigmoid and one store per pair (lane group nb stores block nb:
+// 64 consecutive bytes).  A pair's sums depend on its column only through which lane holds it,
+// never on the tile, the wave or the batch: equal pairs give equal bits anywhere.
+constexpr int kPairTile = RG_NCF_SCORE_PAIR_TILE, PNB = kPairTile / (16 * kWaves);
+static_assert(PNB * 16 * kWaves == kPairTile && PNB >= 1 && PNB <= 4, "header constant");
+
+template <int E>
+struct PairShape {        // LDS (floats): weights of the MFMA layers 0 .. NH - 1, their biases, the output row, its GMF columns
+    using S = Shape<E>;
+    static constexpr int lw_off(int k) {
+        int o = 0;
+        for (int j = 0; j < k; ++j) o += S::rows(j) * S::S(j);
+        return o;
+    }
+    static constexpr int lb_off(int k) {
+        int o = lw_off(S::NH);
+        for (int j = 0; j < k; ++j) o += S::rows(j);
+        return o;
+    }
+    static constexpr int oWo = lb_off(S::NH), oAw = oWo + 16;
+    static constexpr int lds_floats(int mp) { return oAw + mp; }
+};
+
+struct PairArgs {
+    const float *user_w, *item_w, *mlp, *mf_user_w, *mf_item_w;
+    const int64_t *users, *items;
+    int64_t n, tiles;
+    int M, MP;
+    float *out;
+};
+
+template <int E>
+__global__ __launch_bounds__(kThreads, 2) void ncf_score_pairs_kernel(PairArgs a) {
+    using S = Shape<E>;
+    using L = PairShape<E>;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, j = lane & 15;
+
+    // ---- stage: every layer's weights and biases (zero padded), the output row, the GMF columns
+    static_for<S::NH>([&](auto kc) {
+        constexpr int K = decltype(kc)::value, in = S::H(K), out = S::H(K + 1), R = S::rows(K), St = S::S(K);
+        const float *Wg = a.mlp + S::w_off(K);
+        for (int idx = tid; idx < R * St; idx += kThreads) {
+            const int r = idx / St, c = idx % St;
+            lds[L::lw_off(K) + idx] = r < out && c < in ? Wg[r * in + c] : 0.0f;
+        }
+        for (int idx = tid; idx < R; idx += kThreads) lds[L::lb_off(K) + idx] = idx < out ? Wg[out * in + idx] : 0.0f;
+    });
+    const float *aff = a.mlp + S::w_off(S::NH);
+    if (tid < 16) lds[L::oWo + tid] = tid < 8 ? aff[tid] : 0.0f;
+    for (int idx = tid; idx < a.MP; idx += kThreads) lds[L::oAw + idx] = idx < a.M ? aff[8 + idx] : 0.0f;
+    const float bo = aff[8 + a.M];
+    __syncthreads();                       // the only barrier
+    const v4f wo = *reinterpret_cast<const v4f *>(lds + L::oWo + 4 * g);
+    const float *aw = lds + L::oAw;
+
+    constexpr int T0 = S::tiles(0);
+    for (int64_t tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
+        const int64_t p0 = tile * kPairTile + wave * (16 * PNB);      // this wave's first pair
+        if (p0 >= a.n) break;                                         // wave-uniform; later tiles lie further out
+        // ---- gather (pairs past n read pair n - 1; masked at the store)
+        int64_t u[PNB], it[PNB];
+#pragma unroll
+        for (int nb = 0; nb < PNB; ++nb) {
+            int64_t p = p0 + 16 * nb + j;
+            p = p < a.n ? p : a.n - 1;
+            u[nb] = a.users[p];
+            it[nb] = a.items[p];
+        }
+        v4f x[T0][PNB];
+#pragma unroll
+        for (int t = 0; t < T0; ++t) {
+            const int f = 16 * t + 4 * g;                             // < E: the user's row, else the item's
+#pragma unroll
+            for (int nb = 0; nb < PNB; ++nb)
+                x[t][nb] = *reinterpret_cast<const v4f *>(f < E ? a.user_w + u[nb] * E + f : a.item_w + it[nb] * E + (f - E));
+        }
+        v4f last[PNB];
+        tower<E, 0, L, PNB>(x, last, lds, g, j);
+
+        // ---- this lane group's quarter of the logit: output dot, then the GMF columns c = g mod 4
+        float p[PNB];
+#pragma unroll
+        for (int nb = 0; nb < PNB; ++nb)
+            p[nb] = fmaf(wo[3], last[nb][3], fmaf(wo[2], last[nb][2], fmaf(wo[1], last[nb][1], wo[0] * last[nb][0])));
+        if (a.M > 0) {
+            const float *mu[PNB], *mi[PNB];
+#pragma unroll
+            for (int nb = 0; nb < PNB; ++nb) {
+                mu[nb] = a.mf_user_w + u[nb] * a.M;
+                mi[nb] = a.mf_item_w + it[nb] * a.M;
+            }
+#pragma unroll 4
+            for (int k = 0; k < a.MP; k += 4) {
+                const int c = k + g, cc = c < a.M ? c : a.M - 1;      // padding columns: read in bounds, not added
+                const float w = aw[c];
+#pragma unroll
+                for (int nb = 0; nb < PNB; ++nb) {
+                    const float q = fmaf(w * mu[nb][cc], mi[nb][cc], p[nb]);
+                    p[nb] = c < a.M ? q : p[nb];
+                }
+            }
+        }
+        float z = 0.0f;
+#pragma unroll
+        for (int nb = 0; nb < PNB; ++nb) {
+            float s = p[nb];
+            s += __shfl_xor(s, 16);
+            s += __shfl_xor(s, 32);
+            z = g == nb ? s : z;
+        }
+        // ---- bias, sigmoid, store: lane group nb stores block nb
+        const int64_t po = p0 + 16 * g + j;
+        if (g < PNB && po < a.n) a.out[po] = sigmoidf_ref(z + bo);
+    }
+}
+
 int score_check_model(const rg_ncf_model_t *m, int64_t n_users, const char *who) {
     const std::string w(who);
     if (!m) return fail_arg(w + ": null model");
@@ -314,10 +446,57 @@ int score_launch(hipStream_t s, const rg_ncf_model_t *m, const int64_t *users, i
     return check_launch("rg_ncf_score_users");
 }
 
+// workgroups that are resident at once (LDS and registers of the compiled kernel): the grid's cap, so
+// every workgroup stages the weights once and the tiles spread evenly over one resident set
+template <int E>
+int pairs_resident(int MP) {
+    static int per_cu[RG_NEUMF_MAX_MF_DIM / 4 + 1] = {};
+    int &k = per_cu[MP / 4];
+    if (k == 0) {
+        int b = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, ncf_score_pairs_kernel<E>, kThreads,
+                                                         PairShape<E>::lds_floats(MP) * sizeof(float)) != hipSuccess || b < 1)
+            b = 1;
+        k = b > 8 ? 8 : b;
+    }
+    return k * num_cus();
+}
+
+template <int E>
+int pairs_launch(hipStream_t s, const rg_ncf_model_t *m, const int64_t *users, const int64_t *items, int64_t n, float *out) {
+    const int MP = pad4(m->mf_dim);
+    const int64_t tiles = (n + kPairTile - 1) / kPairTile, cap = pairs_resident<E>(MP);
+    const PairArgs a{m->user_w, m->item_w, m->mlp, m->mf_user_w, m->mf_item_w, users, items, n, tiles, m->mf_dim, MP, out};
+    hipLaunchKernelGGL((ncf_score_pairs_kernel<E>), dim3((unsigned)(tiles < cap ? tiles : cap)), dim3(kThreads),
+                       PairShape<E>::lds_floats(MP) * sizeof(float), s, a);
+    return check_launch("rg_ncf_score_pairs");
+}
+
 }  // namespace
 }  // namespace rg
 
 using namespace rg;
+
+extern "C" int rg_ncf_score_pairs(void *stream, const rg_ncf_model_t *m, const int64_t *users_dev, const int64_t *items_dev,
+                                  int64_t n, float *out_dev) {
+    if (!m) return fail_arg("rg_ncf_score_pairs: null model");
+    if (rg_ncf_mlp_len(m->dim) < 0) return fail_arg("rg_ncf_score_pairs: dim must be 8, 16, 32 or 64");
+    if (m->mf_dim < 0 || m->mf_dim > RG_NEUMF_MAX_MF_DIM) return fail_arg("rg_ncf_score_pairs: mf_dim out of range");
+    if (n < 0) return fail_arg("rg_ncf_score_pairs: n < 0");
+    if (!users_dev || !items_dev || !out_dev || !m->user_w || !m->item_w || !m->mlp)
+        return fail_arg("rg_ncf_score_pairs: null argument");
+    if (m->mf_dim > 0 && (!m->mf_user_w || !m->mf_item_w)) return fail_arg("rg_ncf_score_pairs: mf_dim > 0 without the GMF tables");
+    if ((uintptr_t)m->user_w % 16 || (uintptr_t)m->item_w % 16)
+        return fail_arg("rg_ncf_score_pairs: the embedding tables must be 16-byte aligned");
+    if (n == 0) return RG_OK;
+    const hipStream_t s = (hipStream_t)stream;
+    switch (m->dim) {
+        case 8: return pairs_launch<8>(s, m, users_dev, items_dev, n, out_dev);
+        case 16: return pairs_launch<16>(s, m, users_dev, items_dev, n, out_dev);
+        case 32: return pairs_launch<32>(s, m, users_dev, items_dev, n, out_dev);
+        default: return pairs_launch<64>(s, m, users_dev, items_dev, n, out_dev);
+    }
+}
 
 extern "C" int64_t rg_ncf_score_workspace_len(const rg_ncf_model_t *m, int64_t n_users) {
     if (score_check_model(m, n_users, "rg_ncf_score_workspace_len") != RG_OK) return -1;

@@ -7,7 +7,7 @@ Times, for the E = 64 NCF MLP and NeuMF (E = 16, M = 50) at the ML-20M item coun
 
   * ``NCFEngine.score_users``  -- rg_ncf_score_users (the split first layer's halves + the fused
     pair kernel), and
-  * ``NCFEngine.scores``       -- the pairwise torch path the evaluation used before (gather, cat,
+  * ``NCFEngine.scores_torch`` -- the pairwise torch path the evaluation used before (gather, cat,
     one GEMM per layer, where, sigmoid through global memory),
 
 with device events around each call after a warm-up, the two paths alternating, and reports
@@ -34,6 +34,16 @@ device path (``CGAN.test``: rg_gan_generate per batch, one rg_slate_hits launch,
 the host path it replaced (per batch a GANBatch, ``generate``, ``.cpu()`` and the per-user set
 loop, restated here) run in the same process on the same engine under the same torch seed, wall
 time around calls that end on the host; the two results must be equal.
+
+    python -m recommendation_gans_amd.eval_time --metric pairs [--users 256] [--batch 8192] [--reps 5]
+
+times the scores of arbitrary (user, item) pairs, ``NCFEngine.scores`` (rg_ncf_score_pairs, one
+fused launch) against ``NCFEngine.scores_torch`` (the chain of torch ops it replaced) on the same
+engine and ids, for the same two models at two sizes: the ``--users`` x ``--items`` block as a flat
+list of pairs, and one training batch of ``--batch`` random pairs.  Device events, the two paths
+alternating; min / median, the largest relative difference of the two results, and the kernel's
+time against max(flops at the fp32 MFMA peak, gathered bytes at the HBM peak).  One JSON line per
+model and size.
 """
 import argparse
 import json
@@ -268,9 +278,61 @@ def main_slates(args):
     return [r]
 
 
+def pairs_algorithmic(E, M, n):
+    """Flops (2 per MAC; the GMF term 3 per column) and compulsory bytes (ids in, gathered rows, one
+    score out) of n pairs on rg_ncf_score_pairs."""
+    sizes = tower(E)
+    macs = sum(i * o for i, o in zip(sizes[:-1], sizes[1:])) + 8
+    return n * (2.0 * macs + 3.0 * M), n * (4.0 * (2 * E + 2 * M) + 16 + 4)
+
+
+def main_pairs(args):
+    """``--metric pairs``: NCFEngine.scores (rg_ncf_score_pairs) against NCFEngine.scores_torch on the
+    same engine and ids, at the users x items block and at one training batch of random pairs."""
+    dev = torch.device("cuda:0")
+    U, I = 138493, args.items
+    out = []
+    for name, E, M in (("ncf_e64", 64, 0), ("neumf_e16_m50", 16, 50)):
+        e = make_engine(E, M, U, I, dev)
+        rs = np.random.RandomState(1)
+        users = torch.from_numpy(rs.randint(0, U, args.users)).to(dev)
+        sizes = [("block", users.repeat_interleave(I), torch.arange(I, device=dev).repeat(args.users)),
+                 ("batch", torch.from_numpy(rs.randint(0, U, args.batch)).to(dev),
+                  torch.from_numpy(rs.randint(0, I, args.batch)).to(dev))]
+        for kind, pu, pi in sizes:
+            n = int(pu.numel())
+            new = lambda: e.scores(pu, pi)
+            old = lambda: e.scores_torch(pu, pi)
+            for _ in range(3):                               # warm-up: code objects, GEMM algorithms, allocator
+                a, b = new(), old()
+            torch.cuda.synchronize()
+            rel = float(((a - b).abs() / b.abs()).max())
+            t_new, t_old = [], []
+            for _ in range(args.reps):                       # alternate the two paths
+                t_new += timed(new, 1)
+                t_old += timed(old, 1)
+            flops, bytes_ = pairs_algorithmic(E, M, n)
+            bound = max(flops / PEAK_FP32_MFMA, bytes_ / PEAK_HBM)
+            r = {"metric": "pairs", "model": name, "size": kind, "pairs": n, "reps": args.reps,
+                 "kernel_ms": {"min": min(t_new), "median": float(np.median(t_new))},
+                 "torch_ms": {"min": min(t_old), "median": float(np.median(t_old))},
+                 "speedup_min": min(t_old) / min(t_new), "speedup_median": float(np.median(t_old) / np.median(t_new)),
+                 "max_rel_diff": rel, "gflop": flops / 1e9, "mbytes": bytes_ / 1e6,
+                 "bound_ms": bound * 1e3,
+                 "bound_by": "flops" if flops / PEAK_FP32_MFMA >= bytes_ / PEAK_HBM else "bytes",
+                 "frac_of_bound": bound / (min(t_new) * 1e-3)}
+            print(json.dumps(r), flush=True)
+            out.append(r)
+            del a, b
+        del e, sizes, pu, pi
+        torch.cuda.empty_cache()
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--metric", choices=("scores", "mrr", "slates"), default="scores")
+    ap.add_argument("--metric", choices=("scores", "mrr", "slates", "pairs"), default="scores")
+    ap.add_argument("--batch", type=int, default=8192)
     ap.add_argument("--users", type=int, default=None)
     ap.add_argument("--hist-len", type=int, default=128)
     ap.add_argument("--items", type=int, default=26744)
@@ -282,7 +344,9 @@ def main(argv=None):
     if args.users is None:
         args.users = ML20M_USERS if slates else 256
     if args.reps is None:
-        args.reps = 5 if slates else 20
+        args.reps = 5 if slates or args.metric == "pairs" else 20
+    if args.metric == "pairs":
+        return main_pairs(args)
     if args.metric == "mrr":
         return main_mrr(args)
     if slates:
@@ -295,7 +359,7 @@ def main(argv=None):
         users = torch.from_numpy(np.random.RandomState(1).randint(0, U, n)).to(dev)
         pu, pi = users.repeat_interleave(I), torch.arange(I, device=dev).repeat(n)
         new = lambda: e.score_users(users)
-        old = lambda: e.scores(pu, pi)
+        old = lambda: e.scores_torch(pu, pi)
         for _ in range(3):                                   # warm-up: code objects, GEMM algorithms, allocator
             a, b = new(), old().reshape(n, I)
         torch.cuda.synchronize()

@@ -445,7 +445,30 @@ class NCFEngine:
             dst.copy_(torch.as_tensor(src, dtype=torch.float32).reshape(dst.shape))
 
     def scores(self, users, items):
-        """Eval-mode scores (no dropout) for (user, item) pairs, on the device."""
+        """Eval-mode scores (no dropout) for (user, item) pairs, on the device: one fused launch
+        (rg_ncf_score_pairs: gathers, every layer on the MFMA, sigmoid; no activation leaves the
+        chip).  A pair's score is the same bits wherever it stands in the batch."""
+        users = torch.as_tensor(users).to(self.device, torch.int64).reshape(-1).contiguous()
+        items = torch.as_tensor(items).to(self.device, torch.int64).reshape(-1).contiguous()
+        n = int(users.numel())
+        if int(items.numel()) != n:
+            raise ValueError("users and items differ in length")
+        out = torch.empty(n, dtype=torch.float32, device=self.device)
+        if n == 0:
+            return out
+        # one download for the four bounds
+        ulo, uhi, ilo, ihi = torch.stack([*users.aminmax(), *items.aminmax()]).tolist()
+        if ulo < 0 or uhi >= self.U:
+            raise ValueError("user ids outside the user table")
+        if ilo < 0 or ihi >= self.I:
+            raise ValueError("item ids outside the item table")
+        check(self.lib.rg_ncf_score_pairs(_lib.stream_handle(), ctypes.byref(self._model), ptr(users), ptr(items), n,
+                                          ptr(out)), "rg_ncf_score_pairs")
+        return out
+
+    def scores_torch(self, users, items):
+        """The same scores as a chain of torch ops (gather, cat, one GEMM per layer, where,
+        sigmoid): the timing baseline and test yardstick of ``scores``."""
         users = torch.as_tensor(users).to(self.device, torch.int64).reshape(-1)
         items = torch.as_tensor(items).to(self.device, torch.int64).reshape(-1)
         x = torch.cat([self.user_w[users], self.item_w[items]], 1)
