@@ -26,6 +26,7 @@
 #include <utility>
 
 #include "rg_common.h"
+#include "rg_mfma.h"
 #include "rg_mlp_update.h"
 
 namespace rg {
@@ -33,8 +34,6 @@ namespace rg {
 constexpr int kRows = 32;              // examples per tile (two 16-row MFMA tiles)
 constexpr int kNcfThreads = 256;
 constexpr int kNcfCap = RG_MF_LIST_CAP;
-
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 // layer sizes H_k = 2E >> k, k = 0..NH (H_NH = 8); NH hidden Linear layers + output 8 -> 1
 template <int E>
@@ -109,18 +108,6 @@ struct NcfArgs {
 };
 
 enum NcfPhase { kNcfFused = 0, kNcfScores = 1, kNcfGivenDp = 2, kNcfLossOnly = 3 };
-
-// f(integral_constant<int, 0>), ..., f(integral_constant<int, N - 1>): the layer loops
-// contain barriers and were not unrolled, which left every layer's shapes (and so the
-// MFMA K loop) runtime values -- an LDS round trip between consecutive MFMA pairs
-template <class F, int... I>
-__device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F &&f) {
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
 
 // Diagnostic build only (RG_DIAG_STAMPS): s_memrealtime at the tile phase boundaries of
 // the first two tiles of every workgroup (thread 0, after the phase's barrier), for
@@ -872,8 +859,6 @@ __device__ __forceinline__ int at(int row, int col) {
 // order, so a wavefront-scope fence (no wait instruction) is all a cross-lane LDS hand-off
 // inside the wave needs
 __device__ __forceinline__ void wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
-
-__device__ __forceinline__ v4f mfma(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 // Y^T (TO tiles) = W X^T: W [16 TO][16 TI] (row stride S), X^T T-layout (TI tiles)
 template <int TI, int TO>

@@ -31,14 +31,12 @@
 // Arbitrary (user, item) pairs (predict(users, items)) cannot split the first layer; they have a
 // kernel of their own below (rg_ncf_score_pairs), which shares the tower and the LDS weight layout.
 #include <climits>
-#include <utility>
 
 #include "rg_common.h"
+#include "rg_mfma.h"
 
 namespace rg {
 namespace {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 constexpr int kTile = RG_NCF_SCORE_ITEM_TILE, NB = kTile / 16;
 constexpr int kWaves = 4, kThreads = 64 * kWaves, kGroup = 16 * kWaves;
@@ -60,34 +58,41 @@ struct Shape {
         for (int j = 0; j < k; ++j) o += H(j + 1) * H(j) + H(j + 1);
         return o;
     }
-    // LDS (floats): weights of the MFMA layers 1 .. NH - 1, their biases, the output row, Hu rows
+    // a layer in LDS: row-major [rows(k)][S(k)], the rows padded to 16 with zeros
     static constexpr int tiles(int k) { return H(k) < 16 ? 1 : H(k) / 16; }   // 16-feature tiles of layer k's input
     static constexpr int rows(int k) { return 16 * tiles(k + 1); }
     static constexpr int S(int k) { return H(k) + 4; }
+};
+
+// LDS (floats) of a kernel whose first MFMA layer is K0: the weights of layers K0 .. NH - 1, their
+// biases, the 16-float output row; what the kernel stages of its own starts at `end`
+template <int E, int K0>
+struct TowerLds {
+    using S = Shape<E>;
     static constexpr int lw_off(int k) {
         int o = 0;
-        for (int j = 1; j < k; ++j) o += rows(j) * S(j);
+        for (int j = K0; j < k; ++j) o += S::rows(j) * S::S(j);
         return o;
     }
     static constexpr int lb_off(int k) {
-        int o = lw_off(NH);
-        for (int j = 1; j < k; ++j) o += rows(j);
+        int o = lw_off(S::NH);
+        for (int j = K0; j < k; ++j) o += S::rows(j);
         return o;
     }
-    static constexpr int oWo = lb_off(NH), oHu = oWo + 16, oIm = oHu + kGroup * E;
-    static constexpr int lds_floats(int mp) { return oIm + (mp ? kTile * im_stride(mp) : 0); }
+    static constexpr int oWo = lb_off(S::NH), end = oWo + 16;
 };
 
-template <class F, int... I>
-__device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F &&f) {
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
+// a lane's four products of the 8-wide (padded 16) output dot
+__device__ __forceinline__ float out_dot(v4f wo, v4f x) {
+    return fmaf(wo[3], x[3], fmaf(wo[2], x[2], fmaf(wo[1], x[1], wo[0] * x[0])));
 }
 
-__device__ __forceinline__ v4f mfma(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+// sum over the four lane groups (lanes j, 16 + j, 32 + j, 48 + j), left in each of them
+__device__ __forceinline__ float group_sum(float p) {
+    p += __shfl_xor(p, 16);
+    p += __shfl_xor(p, 32);
+    return p;
+}
 
 __device__ __forceinline__ v4f lrelu(v4f z) {
     v4f y;
@@ -156,11 +161,12 @@ struct ScoreArgs {
 
 // layers K .. NH - 1 on the MFMA, x = layer K's input in the T layout (tile t, block nb, register
 // r: feature 16 t + 4 g + r of item 16 nb + j); last = the 8 (padded 16) inputs of the output dot
-// (L: where the layers' weights and biases sit in LDS; N: 16-column blocks per wave)
-template <int E, int K, class L = Shape<E>, int N = NB>
+// (K0: the kernel's first MFMA layer, which fixes the LDS layout; N: 16-column blocks per wave)
+template <int E, int K0, int N, int K = K0>
 __device__ __forceinline__ void tower(const v4f (&x)[Shape<E>::tiles(K)][N], v4f (&last)[N], const float *lds, int g,
                                       int m) {
     using S = Shape<E>;
+    using L = TowerLds<E, K0>;
     if constexpr (K == S::NH) {
 #pragma unroll
         for (int nb = 0; nb < N; ++nb) last[nb] = x[0][nb];
@@ -190,13 +196,21 @@ __device__ __forceinline__ void tower(const v4f (&x)[Shape<E>::tiles(K)][N], v4f
         for (int t = 0; t < TO; ++t)
 #pragma unroll
             for (int nb = 0; nb < N; ++nb) y[t][nb] = lrelu(y[t][nb]);
-        tower<E, K + 1, L, N>(y, last, lds, g, m);
+        tower<E, K0, N, K + 1>(y, last, lds, g, m);
     }
 }
+
+// the all-item kernel's LDS: the tower from layer 1, the group's Hu rows, the tile's mf_item rows
+template <int E>
+struct ScoreLds : TowerLds<E, 1> {
+    static constexpr int oHu = TowerLds<E, 1>::end, oIm = oHu + kGroup * E;
+    static constexpr int lds_floats(int mp) { return oIm + (mp ? kTile * im_stride(mp) : 0); }
+};
 
 template <int E>
 __global__ __launch_bounds__(kThreads, 2) void ncf_score_kernel(ScoreArgs a) {
     using S = Shape<E>;
+    using L = ScoreLds<E>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, j = lane & 15;
     const int64_t i0 = (int64_t)blockIdx.x * kTile, u0 = (int64_t)blockIdx.y * kGroup;
@@ -209,19 +223,19 @@ __global__ __launch_bounds__(kThreads, 2) void ncf_score_kernel(ScoreArgs a) {
         const float *Wg = a.mlp + S::w_off(K);
         for (int idx = tid; idx < R * St; idx += kThreads) {
             const int r = idx / St, c = idx % St;
-            lds[S::lw_off(K) + idx] = r < out && c < in ? Wg[r * in + c] : 0.0f;
+            lds[L::lw_off(K) + idx] = r < out && c < in ? Wg[r * in + c] : 0.0f;
         }
-        for (int idx = tid; idx < R; idx += kThreads) lds[S::lb_off(K) + idx] = idx < out ? Wg[out * in + idx] : 0.0f;
+        for (int idx = tid; idx < R; idx += kThreads) lds[L::lb_off(K) + idx] = idx < out ? Wg[out * in + idx] : 0.0f;
     });
-    if (tid < 16) lds[S::oWo + tid] = tid < 8 ? a.mlp[S::w_off(S::NH) + tid] : 0.0f;
+    if (tid < 16) lds[L::oWo + tid] = tid < 8 ? a.mlp[S::w_off(S::NH) + tid] : 0.0f;
     for (int idx = tid; idx < kGroup * E; idx += kThreads) {
         const int64_t u = u0 + idx / E;
-        lds[S::oHu + idx] = u < a.n_users ? a.Hu[u * E + idx % E] : 0.0f;
+        lds[L::oHu + idx] = u < a.n_users ? a.Hu[u * E + idx % E] : 0.0f;
     }
     if (a.M > 0)
         for (int idx = tid; idx < kTile * SM; idx += kThreads) {
             const int r = idx / SM, c = idx % SM;
-            lds[S::oIm + idx] = i0 + r < a.num_items && c < a.M ? a.mf_item_w[(i0 + r) * a.M + c] : 0.0f;
+            lds[L::oIm + idx] = i0 + r < a.num_items && c < a.M ? a.mf_item_w[(i0 + r) * a.M + c] : 0.0f;
         }
     const float bo = a.mlp[S::w_off(S::NH) + 8 + a.M];
     __syncthreads();                       // the only barrier: a wave without users may leave now
@@ -239,7 +253,7 @@ __global__ __launch_bounds__(kThreads, 2) void ncf_score_kernel(ScoreArgs a) {
 #pragma unroll
         for (int t = 0; t < T0; ++t) hi[t][nb] = *reinterpret_cast<const v4f *>(a.Hi + item * E + 16 * t + fcol);
     }
-    const v4f wo = *reinterpret_cast<const v4f *>(lds + S::oWo + 4 * g);
+    const v4f wo = *reinterpret_cast<const v4f *>(lds + L::oWo + 4 * g);
 
     // ---- the tower, one user at a time; acc[nb][r] = logit of (user uw + 4 g + r, item 16 nb + j)
     v4f acc[NB];
@@ -248,7 +262,7 @@ __global__ __launch_bounds__(kThreads, 2) void ncf_score_kernel(ScoreArgs a) {
 #pragma unroll 1
     for (int uu = 0; uu < 16; ++uu) {
         if (uw + uu >= a.n_users) break;               // wave-uniform
-        const float *hu = lds + S::oHu + (wave * 16 + uu) * E;
+        const float *hu = lds + L::oHu + (wave * 16 + uu) * E;
         v4f x[T0][NB];
 #pragma unroll
         for (int t = 0; t < T0; ++t) {
@@ -257,12 +271,10 @@ __global__ __launch_bounds__(kThreads, 2) void ncf_score_kernel(ScoreArgs a) {
             for (int nb = 0; nb < NB; ++nb) x[t][nb] = lrelu(hi[t][nb] + h);
         }
         v4f last[NB];
-        tower<E, 1>(x, last, lds, g, j);
+        tower<E, 1, NB>(x, last, lds, g, j);
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) {
-            float p = fmaf(wo[3], last[nb][3], fmaf(wo[2], last[nb][2], fmaf(wo[1], last[nb][1], wo[0] * last[nb][0])));
-            p += __shfl_xor(p, 16);
-            p += __shfl_xor(p, 32);
+            const float p = group_sum(out_dot(wo, last[nb]));
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[nb][r] = 4 * g + r == uu ? p : acc[nb][r];
         }
@@ -273,7 +285,7 @@ __global__ __launch_bounds__(kThreads, 2) void ncf_score_kernel(ScoreArgs a) {
         int64_t um = uw + j;
         um = um < a.n_users ? um : a.n_users - 1;
         const float *gp = a.Gu + um * a.MP + g;
-        const float *ip = lds + S::oIm + j * SM + g;
+        const float *ip = lds + L::oIm + j * SM + g;
         for (int k = 0; k < a.MP; k += 4) {
             const float av = gp[k];
 #pragma unroll
@@ -311,20 +323,10 @@ __global__ __launch_bounds__(kThreads, 2) void ncf_score_kernel(ScoreArgs a) {
 constexpr int kPairTile = RG_NCF_SCORE_PAIR_TILE, PNB = kPairTile / (16 * kWaves);
 static_assert(PNB * 16 * kWaves == kPairTile && PNB >= 1 && PNB <= 4, "header constant");
 
+// the pair kernel's LDS: the whole tower, the output row's GMF columns
 template <int E>
-struct PairShape {        // LDS (floats): weights of the MFMA layers 0 .. NH - 1, their biases, the output row, its GMF columns
-    using S = Shape<E>;
-    static constexpr int lw_off(int k) {
-        int o = 0;
-        for (int j = 0; j < k; ++j) o += S::rows(j) * S::S(j);
-        return o;
-    }
-    static constexpr int lb_off(int k) {
-        int o = lw_off(S::NH);
-        for (int j = 0; j < k; ++j) o += S::rows(j);
-        return o;
-    }
-    static constexpr int oWo = lb_off(S::NH), oAw = oWo + 16;
+struct PairLds : TowerLds<E, 0> {
+    static constexpr int oAw = TowerLds<E, 0>::end;
     static constexpr int lds_floats(int mp) { return oAw + mp; }
 };
 
@@ -339,7 +341,7 @@ struct PairArgs {
 template <int E>
 __global__ __launch_bounds__(kThreads, 2) void ncf_score_pairs_kernel(PairArgs a) {
     using S = Shape<E>;
-    using L = PairShape<E>;
+    using L = PairLds<E>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, j = lane & 15;
 
@@ -383,13 +385,12 @@ __global__ __launch_bounds__(kThreads, 2) void ncf_score_pairs_kernel(PairArgs a
                 x[t][nb] = *reinterpret_cast<const v4f *>(f < E ? a.user_w + u[nb] * E + f : a.item_w + it[nb] * E + (f - E));
         }
         v4f last[PNB];
-        tower<E, 0, L, PNB>(x, last, lds, g, j);
+        tower<E, 0, PNB>(x, last, lds, g, j);
 
         // ---- this lane group's quarter of the logit: output dot, then the GMF columns c = g mod 4
         float p[PNB];
 #pragma unroll
-        for (int nb = 0; nb < PNB; ++nb)
-            p[nb] = fmaf(wo[3], last[nb][3], fmaf(wo[2], last[nb][2], fmaf(wo[1], last[nb][1], wo[0] * last[nb][0])));
+        for (int nb = 0; nb < PNB; ++nb) p[nb] = out_dot(wo, last[nb]);
         if (a.M > 0) {
             const float *mu[PNB], *mi[PNB];
 #pragma unroll
@@ -411,9 +412,7 @@ __global__ __launch_bounds__(kThreads, 2) void ncf_score_pairs_kernel(PairArgs a
         float z = 0.0f;
 #pragma unroll
         for (int nb = 0; nb < PNB; ++nb) {
-            float s = p[nb];
-            s += __shfl_xor(s, 16);
-            s += __shfl_xor(s, 32);
+            const float s = group_sum(p[nb]);
             z = g == nb ? s : z;
         }
         // ---- bias, sigmoid, store: lane group nb stores block nb
@@ -422,29 +421,58 @@ __global__ __launch_bounds__(kThreads, 2) void ncf_score_pairs_kernel(PairArgs a
     }
 }
 
-int score_check_model(const rg_ncf_model_t *m, int64_t n_users, const char *who) {
-    const std::string w(who);
+// The model check of the three entry points.  The shape part reads no pointer of the model
+// (rg_ncf_score_workspace_len sizes a model whose tables do not exist yet); `count` names n.
+int score_check_shape(const rg_ncf_model_t *m, int64_t n, const char *count, const std::string &w) {
     if (!m) return fail_arg(w + ": null model");
     if (rg_ncf_mlp_len(m->dim) < 0) return fail_arg(w + ": dim must be 8, 16, 32 or 64");
     if (m->mf_dim < 0 || m->mf_dim > RG_NEUMF_MAX_MF_DIM) return fail_arg(w + ": mf_dim out of range");
     if (m->num_items < 1 || m->num_users < 1) return fail_arg(w + ": empty tables");
-    if (n_users < 0) return fail_arg(w + ": n_users < 0");
+    if (n < 0) return fail_arg(w + ": " + count + " < 0");
     return RG_OK;
 }
 
-template <int E>
-int score_launch(hipStream_t s, const rg_ncf_model_t *m, const int64_t *users, int64_t n_users, float *ws, float *out,
-                 int64_t ld) {
-    const int MP = pad4(m->mf_dim);
-    float *Hi = ws, *Hu = Hi + m->num_items * E, *Gu = Hu + n_users * E;
-    const HalvesArgs h{m->user_w, m->item_w, m->mlp, m->mf_user_w, users, m->num_items, n_users, m->mf_dim, MP, Hi, Hu, Gu};
-    const int64_t hblocks = (m->num_items + kHalfRows - 1) / kHalfRows + (n_users + kHalfRows - 1) / kHalfRows;
-    hipLaunchKernelGGL((ncf_score_halves_kernel<E>), dim3((unsigned)hblocks), dim3(kThreads), 0, s, h);
-    const ScoreArgs a{m->mlp, Hi, Hu, Gu, m->mf_item_w, m->num_items, n_users, ld, m->mf_dim, MP, out};
-    const dim3 grid((unsigned)((m->num_items + kTile - 1) / kTile), (unsigned)((n_users + kGroup - 1) / kGroup));
-    hipLaunchKernelGGL((ncf_score_kernel<E>), grid, dim3(kThreads), Shape<E>::lds_floats(MP) * sizeof(float), s, a);
-    return check_launch("rg_ncf_score_users");
+// The shape part, then the pointers: the model's tables and `args` (whether the call's own pointers
+// are all there).
+int score_check_model(const rg_ncf_model_t *m, int64_t n, const char *count, bool args, const std::string &w) {
+    const int rc = score_check_shape(m, n, count, w);
+    if (rc != RG_OK) return rc;
+    if (!args || !m->user_w || !m->item_w || !m->mlp) return fail_arg(w + ": null argument");
+    if (m->mf_dim > 0 && (!m->mf_user_w || !m->mf_item_w)) return fail_arg(w + ": mf_dim > 0 without the GMF tables");
+    return RG_OK;
 }
+
+// Dispatch on the embedding width: calls f.template operator()<E>() (dim as score_check_shape left it).
+template <typename F>
+int dispatch_width(int dim, F &&f) {
+    switch (dim) {
+        case 8: return f.template operator()<8>();
+        case 16: return f.template operator()<16>();
+        case 32: return f.template operator()<32>();
+        default: return f.template operator()<64>();
+    }
+}
+
+struct ScoreLaunch {
+    hipStream_t s;
+    const rg_ncf_model_t *m;
+    const int64_t *users;
+    int64_t n_users;
+    float *ws, *out;
+    int64_t ld;
+    template <int E>
+    int operator()() const {
+        const int MP = pad4(m->mf_dim);
+        float *Hi = ws, *Hu = Hi + m->num_items * E, *Gu = Hu + n_users * E;
+        const HalvesArgs h{m->user_w, m->item_w, m->mlp, m->mf_user_w, users, m->num_items, n_users, m->mf_dim, MP, Hi, Hu, Gu};
+        const int64_t hblocks = (m->num_items + kHalfRows - 1) / kHalfRows + (n_users + kHalfRows - 1) / kHalfRows;
+        hipLaunchKernelGGL((ncf_score_halves_kernel<E>), dim3((unsigned)hblocks), dim3(kThreads), 0, s, h);
+        const ScoreArgs a{m->mlp, Hi, Hu, Gu, m->mf_item_w, m->num_items, n_users, ld, m->mf_dim, MP, out};
+        const dim3 grid((unsigned)((m->num_items + kTile - 1) / kTile), (unsigned)((n_users + kGroup - 1) / kGroup));
+        hipLaunchKernelGGL((ncf_score_kernel<E>), grid, dim3(kThreads), ScoreLds<E>::lds_floats(MP) * sizeof(float), s, a);
+        return check_launch("rg_ncf_score_users");
+    }
+};
 
 // workgroups that are resident at once (LDS and registers of the compiled kernel): the grid's cap, so
 // every workgroup stages the weights once and the tiles spread evenly over one resident set
@@ -455,22 +483,29 @@ int pairs_resident(int MP) {
     if (k == 0) {
         int b = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, ncf_score_pairs_kernel<E>, kThreads,
-                                                         PairShape<E>::lds_floats(MP) * sizeof(float)) != hipSuccess || b < 1)
+                                                         PairLds<E>::lds_floats(MP) * sizeof(float)) != hipSuccess || b < 1)
             b = 1;
         k = b > 8 ? 8 : b;
     }
     return k * num_cus();
 }
 
-template <int E>
-int pairs_launch(hipStream_t s, const rg_ncf_model_t *m, const int64_t *users, const int64_t *items, int64_t n, float *out) {
-    const int MP = pad4(m->mf_dim);
-    const int64_t tiles = (n + kPairTile - 1) / kPairTile, cap = pairs_resident<E>(MP);
-    const PairArgs a{m->user_w, m->item_w, m->mlp, m->mf_user_w, m->mf_item_w, users, items, n, tiles, m->mf_dim, MP, out};
-    hipLaunchKernelGGL((ncf_score_pairs_kernel<E>), dim3((unsigned)(tiles < cap ? tiles : cap)), dim3(kThreads),
-                       PairShape<E>::lds_floats(MP) * sizeof(float), s, a);
-    return check_launch("rg_ncf_score_pairs");
-}
+struct PairsLaunch {
+    hipStream_t s;
+    const rg_ncf_model_t *m;
+    const int64_t *users, *items;
+    int64_t n;
+    float *out;
+    template <int E>
+    int operator()() const {
+        const int MP = pad4(m->mf_dim);
+        const int64_t tiles = (n + kPairTile - 1) / kPairTile, cap = pairs_resident<E>(MP);
+        const PairArgs a{m->user_w, m->item_w, m->mlp, m->mf_user_w, m->mf_item_w, users, items, n, tiles, m->mf_dim, MP, out};
+        hipLaunchKernelGGL((ncf_score_pairs_kernel<E>), dim3((unsigned)(tiles < cap ? tiles : cap)), dim3(kThreads),
+                           PairLds<E>::lds_floats(MP) * sizeof(float), s, a);
+        return check_launch("rg_ncf_score_pairs");
+    }
+};
 
 }  // namespace
 }  // namespace rg
@@ -479,47 +514,27 @@ using namespace rg;
 
 extern "C" int rg_ncf_score_pairs(void *stream, const rg_ncf_model_t *m, const int64_t *users_dev, const int64_t *items_dev,
                                   int64_t n, float *out_dev) {
-    if (!m) return fail_arg("rg_ncf_score_pairs: null model");
-    if (rg_ncf_mlp_len(m->dim) < 0) return fail_arg("rg_ncf_score_pairs: dim must be 8, 16, 32 or 64");
-    if (m->mf_dim < 0 || m->mf_dim > RG_NEUMF_MAX_MF_DIM) return fail_arg("rg_ncf_score_pairs: mf_dim out of range");
-    if (n < 0) return fail_arg("rg_ncf_score_pairs: n < 0");
-    if (!users_dev || !items_dev || !out_dev || !m->user_w || !m->item_w || !m->mlp)
-        return fail_arg("rg_ncf_score_pairs: null argument");
-    if (m->mf_dim > 0 && (!m->mf_user_w || !m->mf_item_w)) return fail_arg("rg_ncf_score_pairs: mf_dim > 0 without the GMF tables");
+    const int rc = score_check_model(m, n, "n", users_dev && items_dev && out_dev, "rg_ncf_score_pairs");
+    if (rc != RG_OK) return rc;
     if ((uintptr_t)m->user_w % 16 || (uintptr_t)m->item_w % 16)
         return fail_arg("rg_ncf_score_pairs: the embedding tables must be 16-byte aligned");
     if (n == 0) return RG_OK;
-    const hipStream_t s = (hipStream_t)stream;
-    switch (m->dim) {
-        case 8: return pairs_launch<8>(s, m, users_dev, items_dev, n, out_dev);
-        case 16: return pairs_launch<16>(s, m, users_dev, items_dev, n, out_dev);
-        case 32: return pairs_launch<32>(s, m, users_dev, items_dev, n, out_dev);
-        default: return pairs_launch<64>(s, m, users_dev, items_dev, n, out_dev);
-    }
+    return dispatch_width(m->dim, PairsLaunch{(hipStream_t)stream, m, users_dev, items_dev, n, out_dev});
 }
 
 extern "C" int64_t rg_ncf_score_workspace_len(const rg_ncf_model_t *m, int64_t n_users) {
-    if (score_check_model(m, n_users, "rg_ncf_score_workspace_len") != RG_OK) return -1;
+    if (score_check_shape(m, n_users, "n_users", "rg_ncf_score_workspace_len") != RG_OK) return -1;
     return (m->num_items + n_users) * m->dim + n_users * pad4(m->mf_dim);
 }
 
 extern "C" int rg_ncf_score_users(void *stream, const rg_ncf_model_t *m, const int64_t *users_dev, int64_t n_users,
                                   float *workspace_dev, float *out_dev, int64_t ld) {
-    const int rc = score_check_model(m, n_users, "rg_ncf_score_users");
+    const int rc = score_check_model(m, n_users, "n_users", users_dev && workspace_dev && out_dev, "rg_ncf_score_users");
     if (rc != RG_OK) return rc;
-    if (!users_dev || !workspace_dev || !out_dev || !m->user_w || !m->item_w || !m->mlp ||
-        (m->mf_dim > 0 && (!m->mf_user_w || !m->mf_item_w)))
-        return fail_arg("rg_ncf_score_users: null argument");
     if (ld < m->num_items) return fail_arg("rg_ncf_score_users: ld < num_items");
     if ((uintptr_t)workspace_dev % 16) return fail_arg("rg_ncf_score_users: workspace must be 16-byte aligned");
     if (n_users == 0) return RG_OK;
     if ((n_users + kGroup - 1) / kGroup > 65535 || (m->num_items + kHalfRows - 1) / kHalfRows > INT_MAX / 2)
         return fail_arg("rg_ncf_score_users: too many users or items for one launch");
-    const hipStream_t s = (hipStream_t)stream;
-    switch (m->dim) {
-        case 8: return score_launch<8>(s, m, users_dev, n_users, workspace_dev, out_dev, ld);
-        case 16: return score_launch<16>(s, m, users_dev, n_users, workspace_dev, out_dev, ld);
-        case 32: return score_launch<32>(s, m, users_dev, n_users, workspace_dev, out_dev, ld);
-        default: return score_launch<64>(s, m, users_dev, n_users, workspace_dev, out_dev, ld);
-    }
+    return dispatch_width(m->dim, ScoreLaunch{(hipStream_t)stream, m, users_dev, n_users, workspace_dev, out_dev, ld});
 }

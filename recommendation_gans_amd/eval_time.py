@@ -46,29 +46,42 @@ time against max(flops at the fp32 MFMA peak, gathered bytes at the HBM peak).  
 model and size.
 """
 import argparse
+import contextlib
 import json
+import os
+import tempfile
 
 import numpy as np
 import torch
 
 from .ncf_engine import NCFEngine
+from .ncf_spotlight import mlp_layers
 
 PEAK_FP32_MFMA = 157.3e12      # flop/s (spec)
 PEAK_HBM = 8.0e12              # B/s (spec)
 ML20M_USERS = 136677           # synthetic.ML20M["num_users"]
 
 
-def tower(E):
-    sizes = [2 * E]
-    while sizes[-1] > 8:
-        sizes.append(sizes[-1] // 2)
-    return sizes
+def stats(ts):
+    return {"min": min(ts), "median": float(np.median(ts))}
+
+
+@contextlib.contextmanager
+def temp_cwd():
+    """A temporary working directory: the models write their experiment folder under the cwd."""
+    cwd = os.getcwd()
+    with tempfile.TemporaryDirectory() as td:
+        os.chdir(td)
+        try:
+            yield
+        finally:
+            os.chdir(cwd)
 
 
 def make_engine(E, M, U, I, dev):
     """Reference-style init: N(0, 1) embeddings, Xavier-uniform weights, bias 0.01."""
     g = torch.Generator().manual_seed(0)
-    sizes = tower(E)
+    sizes = mlp_layers(E)
     mlp = []
     for i, o in list(zip(sizes[:-1], sizes[1:])) + [(8 + M, 1)]:
         lim = (6.0 / (i + o)) ** 0.5
@@ -80,7 +93,7 @@ def make_engine(E, M, U, I, dev):
 
 def algorithmic(E, M, n, I):
     """Flops and compulsory bytes of one block on the kernel path (2 flops per MAC)."""
-    sizes = tower(E)
+    sizes = mlp_layers(E)
     narrow = sum(i * o for i, o in zip(sizes[1:-1], sizes[2:])) + 8      # per pair, after the split layer
     pair = narrow + M + E                                                 # + GMF dot + the halves' add
     halves = (I + n) * E * E + n * M
@@ -133,7 +146,7 @@ def mrr_model(kind, U, I, train):
             net.item_embeddings.weight.normal_(0, 0.3)
             net.item_biases.weight.normal_()
     else:
-        net = MLP(layers=tower(64), num_users=U, num_items=I, embedding_dim=64)
+        net = MLP(layers=mlp_layers(64), num_users=U, num_items=I, embedding_dim=64)
     model = ImplicitFactorizationModel(loss="pointwise", embedding_dim=64, n_iter=1, batch_size=256,
                                        representation=net, random_state=np.random.RandomState(0),
                                        neg_examples=[(0, 0), (1, 1)], num_negative_samples=3, use_cuda=True)
@@ -158,42 +171,33 @@ def main_mrr(args):
     """``--metric mrr``: evaluation.mrr_score of the same model object on the device path
     (rank_users -> rg_rank_rows) and on the host path (score block to the host, scipy rankdata
     per user; one repetition), 4,096 test users with train exclusions."""
-    import os
-    import tempfile
     from .spotlight import evaluation
     U, I = 138493, args.items
     test, train = mrr_data(U, I, args.test_users)
     out = []
-    cwd = os.getcwd()
-    with tempfile.TemporaryDirectory() as td:
-        os.chdir(td)                           # the model writes its experiment folder under the cwd
-        try:
-            for kind in ("mf_d64", "ncf_e64"):
-                model = mrr_model(kind, U, I, train)
-                evaluation.mrr_score(model, test, train)                         # warm-up
-                t_dev, got = host_timed(lambda: evaluation.mrr_score(model, test, train), args.reps)
-                t_host, ref = host_timed(lambda: evaluation.mrr_score(_HostOnly(model), test, train), 1)
-                # where the device path's time goes: the score block alone (device events), and
-                # rank_users as a whole (score block + CSR upload + rg_rank_rows + counts download)
-                tcsr, xcsr = test.tocsr(), train.tocsr()
-                ub = np.flatnonzero(np.diff(tcsr.indptr) > 0)
-                ud = torch.as_tensor(ub, device=model._engine.device)
-                t_block = [timed(lambda: model._device_scores(ud), 1)[0] for _ in range(args.reps)]
-                t_rank, _ = host_timed(lambda: model.rank_users(ub, tcsr, xcsr), args.reps)
-                r = {"metric": "mrr", "model": kind, "users": U, "items": I, "test_users": int(len(got)),
-                     "test_items": int(len(test)), "train_items": int(len(train)), "reps": args.reps,
-                     "device_ms": {"min": min(t_dev), "median": float(np.median(t_dev))},
-                     "score_block_ms": {"min": min(t_block), "median": float(np.median(t_block))},
-                     "rank_users_ms": {"min": min(t_rank), "median": float(np.median(t_rank))},
-                     "host_ms": t_host[0], "speedup_min": t_host[0] / min(t_dev),
-                     "speedup_median": float(t_host[0] / np.median(t_dev)),
-                     "max_rel_diff": float((np.abs(got - ref) / ref).max()), "mean_mrr": float(got.mean())}
-                print(json.dumps(r), flush=True)
-                out.append(r)
-                del model
-                torch.cuda.empty_cache()
-        finally:
-            os.chdir(cwd)
+    with temp_cwd():
+        for kind in ("mf_d64", "ncf_e64"):
+            model = mrr_model(kind, U, I, train)
+            evaluation.mrr_score(model, test, train)                         # warm-up
+            t_dev, got = host_timed(lambda: evaluation.mrr_score(model, test, train), args.reps)
+            t_host, ref = host_timed(lambda: evaluation.mrr_score(_HostOnly(model), test, train), 1)
+            # where the device path's time goes: the score block alone (device events), and
+            # rank_users as a whole (score block + CSR upload + rg_rank_rows + counts download)
+            tcsr, xcsr = test.tocsr(), train.tocsr()
+            ub = np.flatnonzero(np.diff(tcsr.indptr) > 0)
+            ud = torch.as_tensor(ub, device=model._engine.device)
+            t_block = [timed(lambda: model._device_scores(ud), 1)[0] for _ in range(args.reps)]
+            t_rank, _ = host_timed(lambda: model.rank_users(ub, tcsr, xcsr), args.reps)
+            r = {"metric": "mrr", "model": kind, "users": U, "items": I, "test_users": int(len(got)),
+                 "test_items": int(len(test)), "train_items": int(len(train)), "reps": args.reps,
+                 "device_ms": stats(t_dev), "score_block_ms": stats(t_block), "rank_users_ms": stats(t_rank),
+                 "host_ms": t_host[0], "speedup_min": t_host[0] / min(t_dev),
+                 "speedup_median": float(t_host[0] / np.median(t_dev)),
+                 "max_rel_diff": float((np.abs(got - ref) / ref).max()), "mean_mrr": float(got.mean())}
+            print(json.dumps(r), flush=True)
+            out.append(r)
+            del model
+            torch.cuda.empty_cache()
     return out
 
 
@@ -233,45 +237,37 @@ def host_cgan_test(model, train_vec, test):
 def main_slates(args):
     """``--metric slates``: one CGAN.test of ``--users`` users on the device path and on the host
     path it replaced, same engine, same seed."""
-    import os
-    import tempfile
     from .CGANs import CGAN
     from .spotlight.dnn_models.cGAN_models import discriminator, generator
     from .synthetic import ML20M
     U, N, S, H, E, Z, B, L = args.users, ML20M["num_items"], 5, 256, 5, 100, 256, args.hist_len
     train_vec, test = slates_data(U, N, L)
-    cwd = os.getcwd()
-    with tempfile.TemporaryDirectory() as td:
-        os.chdir(td)                           # the model writes its experiment folder under the cwd
-        try:
-            torch.manual_seed(0)
-            G = generator(num_items=N, noise_dim=Z, embedding_dim=E, hidden_layer=[H // 2, H], output_dim=S)
-            D = discriminator(num_items=N, embedding_dim=E, hidden_layers=[2 * H, H, H // 2], input_dim=S)
-            model = CGAN(G=G, D=D, z_dim=Z, n_iter=1, batch_size=B, slate_size=S, embedding_dim=E, hidden_layer=H,
-                         experiment_name="eval_time", use_cuda=True, random_state=np.random.RandomState(0))
-            model.num_users, model.num_items = U, N
-            model._initialize()
+    with temp_cwd():
+        torch.manual_seed(0)
+        G = generator(num_items=N, noise_dim=Z, embedding_dim=E, hidden_layer=[H // 2, H], output_dim=S)
+        D = discriminator(num_items=N, embedding_dim=E, hidden_layers=[2 * H, H, H // 2], input_dim=S)
+        model = CGAN(G=G, D=D, z_dim=Z, n_iter=1, batch_size=B, slate_size=S, embedding_dim=E, hidden_layer=H,
+                     experiment_name="eval_time", use_cuda=True, random_state=np.random.RandomState(0))
+        model.num_users, model.num_items = U, N
+        model._initialize()
 
-            def seeded(fn):
-                def run():
-                    torch.manual_seed(1)
-                    return fn()
-                return run
+        def seeded(fn):
+            def run():
+                torch.manual_seed(1)
+                return fn()
+            return run
 
-            dev = seeded(lambda: model.test(train_vec, test))
-            host = seeded(lambda: host_cgan_test(model, train_vec, test))
-            dev(), host()                                                        # warm-up
-            host_reps = max(1, min(args.reps, 3))
-            t_dev, got = host_timed(dev, args.reps)
-            t_host, ref = host_timed(host, host_reps)
-        finally:
-            os.chdir(cwd)
+        dev = seeded(lambda: model.test(train_vec, test))
+        host = seeded(lambda: host_cgan_test(model, train_vec, test))
+        dev(), host()                                                        # warm-up
+        host_reps = max(1, min(args.reps, 3))
+        t_dev, got = host_timed(dev, args.reps)
+        t_host, ref = host_timed(host, host_reps)
     if got != ref:
         raise SystemExit(f"the two paths disagree: device {got}, host {ref}")
     r = {"metric": "slates", "users": U, "items": N, "hist_len": L, "slate_size": S, "hidden": H, "emb": E, "z": Z,
          "batch": B, "test_items": int(test.nnz), "reps": args.reps, "host_reps": host_reps,
-         "device_ms": {"min": min(t_dev), "median": float(np.median(t_dev))},
-         "host_ms": {"min": min(t_host), "median": float(np.median(t_host))},
+         "device_ms": stats(t_dev), "host_ms": stats(t_host),
          "speedup_min": min(t_host) / min(t_dev), "speedup_median": float(np.median(t_host) / np.median(t_dev)),
          "results_equal": True, "precision": got["precision"], "recall": got["recall"]}
     print(json.dumps(r), flush=True)
@@ -281,7 +277,7 @@ def main_slates(args):
 def pairs_algorithmic(E, M, n):
     """Flops (2 per MAC; the GMF term 3 per column) and compulsory bytes (ids in, gathered rows, one
     score out) of n pairs on rg_ncf_score_pairs."""
-    sizes = tower(E)
+    sizes = mlp_layers(E)
     macs = sum(i * o for i, o in zip(sizes[:-1], sizes[1:])) + 8
     return n * (2.0 * macs + 3.0 * M), n * (4.0 * (2 * E + 2 * M) + 16 + 4)
 
@@ -314,8 +310,7 @@ def main_pairs(args):
             flops, bytes_ = pairs_algorithmic(E, M, n)
             bound = max(flops / PEAK_FP32_MFMA, bytes_ / PEAK_HBM)
             r = {"metric": "pairs", "model": name, "size": kind, "pairs": n, "reps": args.reps,
-                 "kernel_ms": {"min": min(t_new), "median": float(np.median(t_new))},
-                 "torch_ms": {"min": min(t_old), "median": float(np.median(t_old))},
+                 "kernel_ms": stats(t_new), "torch_ms": stats(t_old),
                  "speedup_min": min(t_old) / min(t_new), "speedup_median": float(np.median(t_old) / np.median(t_new)),
                  "max_rel_diff": rel, "gflop": flops / 1e9, "mbytes": bytes_ / 1e6,
                  "bound_ms": bound * 1e3,
@@ -329,28 +324,9 @@ def main_pairs(args):
     return out
 
 
-def main(argv=None):
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--metric", choices=("scores", "mrr", "slates", "pairs"), default="scores")
-    ap.add_argument("--batch", type=int, default=8192)
-    ap.add_argument("--users", type=int, default=None)
-    ap.add_argument("--hist-len", type=int, default=128)
-    ap.add_argument("--items", type=int, default=26744)
-    ap.add_argument("--reps", type=int, default=None)
-    ap.add_argument("--big", type=int, default=0)
-    ap.add_argument("--test-users", type=int, default=4096)
-    args = ap.parse_args(argv)
-    slates = args.metric == "slates"             # its own defaults: every ML-20M user, 5 repetitions
-    if args.users is None:
-        args.users = ML20M_USERS if slates else 256
-    if args.reps is None:
-        args.reps = 5 if slates or args.metric == "pairs" else 20
-    if args.metric == "pairs":
-        return main_pairs(args)
-    if args.metric == "mrr":
-        return main_mrr(args)
-    if slates:
-        return main_slates(args)
+def main_scores(args):
+    """The default mode: one block of ``--users`` users against every item, NCFEngine.score_users
+    (rg_ncf_score_users) against the pairwise NCFEngine.scores_torch."""
     dev = torch.device("cuda:0")
     U, I, n = 138493, args.items, args.users
     out = []
@@ -372,8 +348,7 @@ def main(argv=None):
         flops, bytes_ = algorithmic(E, M, n, I)
         tn = min(t_new) * 1e-3
         r = {"model": name, "users": n, "items": I, "reps": args.reps,
-             "kernel_ms": {"min": min(t_new), "median": float(np.median(t_new))},
-             "pairwise_ms": {"min": min(t_old), "median": float(np.median(t_old))},
+             "kernel_ms": stats(t_new), "pairwise_ms": stats(t_old),
              "speedup_min": min(t_old) / min(t_new), "speedup_median": float(np.median(t_old) / np.median(t_new)),
              "max_abs_diff": float(diff.max()), "max_rel_diff": rel,
              "gflop": flops / 1e9, "mbytes": bytes_ / 1e6,
@@ -384,7 +359,7 @@ def main(argv=None):
             big()
             tb = timed(big, max(3, args.reps // 4))
             fb, _ = algorithmic(E, M, args.big, I)
-            r["big"] = {"users": args.big, "kernel_ms": {"min": min(tb), "median": float(np.median(tb))},
+            r["big"] = {"users": args.big, "kernel_ms": stats(tb),
                         "frac_fp32_mfma_peak": fb / (min(tb) * 1e-3) / PEAK_FP32_MFMA,
                         "pairwise": "not run: its concatenated input alone is users x items x 2E floats"}
         print(json.dumps(r), flush=True)
@@ -392,6 +367,25 @@ def main(argv=None):
         del e
         torch.cuda.empty_cache()
     return out
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--metric", choices=("scores", "mrr", "slates", "pairs"), default="scores")
+    ap.add_argument("--batch", type=int, default=8192)
+    ap.add_argument("--users", type=int, default=None)
+    ap.add_argument("--hist-len", type=int, default=128)
+    ap.add_argument("--items", type=int, default=26744)
+    ap.add_argument("--reps", type=int, default=None)
+    ap.add_argument("--big", type=int, default=0)
+    ap.add_argument("--test-users", type=int, default=4096)
+    args = ap.parse_args(argv)
+    slates = args.metric == "slates"             # its own defaults: every ML-20M user, 5 repetitions
+    if args.users is None:
+        args.users = ML20M_USERS if slates else 256
+    if args.reps is None:
+        args.reps = 5 if slates or args.metric == "pairs" else 20
+    return {"scores": main_scores, "mrr": main_mrr, "slates": main_slates, "pairs": main_pairs}[args.metric](args)
 
 
 if __name__ == "__main__":

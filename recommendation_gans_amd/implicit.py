@@ -373,6 +373,13 @@ class ImplicitFactorizationModel:
             return torch.sigmoid(U[u] @ I.T + ub[u][:, None] + ib[None, :])
         return self._engine.score_users(u)
 
+    def _score_block(self, users):
+        """(ids as a host int64 array, their contiguous fp32 score block on the device): what the
+        device rankings (topk_users, rank_users) read."""
+        ub = np.asarray(users, dtype=np.int64)
+        u = torch.as_tensor(ub, device=self._engine.device)
+        return ub, self._device_scores(u).to(torch.float32).contiguous()
+
     def score_users(self, users):
         """Scores of every item for a block of users, (len(users), num_items) float32 on
         the host (evaluation helper)."""
@@ -386,9 +393,7 @@ class ImplicitFactorizationModel:
         (len(users), k) int64 on the host."""
         from . import _lib
         dev = self._engine.device
-        ub = np.asarray(users, dtype=np.int64)
-        u = torch.as_tensor(ub, device=dev)
-        s = self._device_scores(u).to(torch.float32).contiguous()
+        ub, s = self._score_block(users)
         if exclude_csr is not None:
             sub = exclude_csr[ub]
             if sub.nnz:
@@ -411,11 +416,10 @@ class ImplicitFactorizationModel:
         read."""
         from . import _lib
         dev = self._engine.device
-        ub = np.asarray(users, dtype=np.int64)
-        t_ptr, t_idx = _csr_rows(targets_csr, ub)
+        t_ptr, t_idx = _csr_rows(targets_csr, np.asarray(users, dtype=np.int64))
         if not len(t_idx):
             return np.zeros(0, dtype=np.float64)
-        s = self._device_scores(torch.as_tensor(ub, device=dev)).to(torch.float32).contiguous()
+        ub, s = self._score_block(users)
         tp, ti = torch.as_tensor(t_ptr, device=dev), torch.as_tensor(t_idx, device=dev)
         ep = ei = None
         if exclude_csr is not None:

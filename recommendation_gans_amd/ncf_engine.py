@@ -444,24 +444,29 @@ class NCFEngine:
         for dst, src in zip(self.params(), tensors):
             dst.copy_(torch.as_tensor(src, dtype=torch.float32).reshape(dst.shape))
 
+    def _ids(self, *lists):
+        """Each (ids, table rows, "user" | "item") as a flat contiguous int64 tensor on the device.
+        Lists of different lengths raise, and so does an id outside its table: one download for
+        every list's bounds."""
+        ids = [torch.as_tensor(x).to(self.device, torch.int64).reshape(-1).contiguous() for x, _, _ in lists]
+        if len({int(t.numel()) for t in ids}) > 1:
+            raise ValueError("users and items differ in length")
+        if ids[0].numel():
+            bounds = torch.stack([b for t in ids for b in t.aminmax()]).tolist()
+            for (_, rows, name), lo, hi in zip(lists, bounds[0::2], bounds[1::2]):
+                if lo < 0 or hi >= rows:
+                    raise ValueError(f"{name} ids outside the {name} table")
+        return ids
+
     def scores(self, users, items):
         """Eval-mode scores (no dropout) for (user, item) pairs, on the device: one fused launch
         (rg_ncf_score_pairs: gathers, every layer on the MFMA, sigmoid; no activation leaves the
         chip).  A pair's score is the same bits wherever it stands in the batch."""
-        users = torch.as_tensor(users).to(self.device, torch.int64).reshape(-1).contiguous()
-        items = torch.as_tensor(items).to(self.device, torch.int64).reshape(-1).contiguous()
+        users, items = self._ids((users, self.U, "user"), (items, self.I, "item"))
         n = int(users.numel())
-        if int(items.numel()) != n:
-            raise ValueError("users and items differ in length")
         out = torch.empty(n, dtype=torch.float32, device=self.device)
         if n == 0:
             return out
-        # one download for the four bounds
-        ulo, uhi, ilo, ihi = torch.stack([*users.aminmax(), *items.aminmax()]).tolist()
-        if ulo < 0 or uhi >= self.U:
-            raise ValueError("user ids outside the user table")
-        if ilo < 0 or ihi >= self.I:
-            raise ValueError("item ids outside the item table")
         check(self.lib.rg_ncf_score_pairs(_lib.stream_handle(), ctypes.byref(self._model), ptr(users), ptr(items), n,
                                           ptr(out)), "rg_ncf_score_pairs")
         return out
@@ -485,13 +490,11 @@ class NCFEngine:
         on the device: rg_ncf_score_users (the split first layer's halves into a cached
         workspace, then the fused pair kernel).  The engine's parameters are read in place, so
         this holds after a data-parallel fit too (every rank has the same replica)."""
-        users = torch.as_tensor(users).to(self.device, torch.int64).reshape(-1).contiguous()
+        users, = self._ids((users, self.U, "user"))
         n = int(users.numel())
         out = torch.empty(n, self.I, dtype=torch.float32, device=self.device)
         if n == 0:
             return out
-        if int(users.min()) < 0 or int(users.max()) >= self.U:
-            raise ValueError("user ids outside the user table")
         need = int(self.lib.rg_ncf_score_workspace_len(ctypes.byref(self._model), n))
         if need < 0:
             raise RuntimeError("rg_ncf_score_workspace_len: " + self.lib.rg_last_error().decode())

@@ -27,12 +27,17 @@ def _row(csr, u):
     return csr.indices[csr.indptr[u]:csr.indptr[u + 1]]
 
 
+def _user_blocks(test_csr, block=4096):
+    """Yields (offset, user block) over the test users with items, in user order, ``block`` at a time."""
+    users = np.flatnonzero(np.diff(test_csr.indptr) > 0)
+    for s in range(0, len(users), block):
+        yield s, users[s:s + block]
+
+
 def _scored(model, test_csr, train_csr=None, block=4096):
     """Yields (user, row indices, -scores with train items at FLOAT_MAX) for every test
     user with items, in user order."""
-    users = np.flatnonzero(np.diff(test_csr.indptr) > 0)
-    for s in range(0, len(users), block):
-        ub = users[s:s + block]
+    for _, ub in _user_blocks(test_csr, block):
         scores = -model.score_users(ub)                      # (len(ub), I) float32, host
         for r, u in enumerate(ub):
             pred = scores[r]
@@ -48,9 +53,7 @@ def _ranked(model, test_csr, train_csr=None, block=4096, k=None):
     """Yields (user, row indices, item ranking) for every test user with items; with k,
     the ranking may hold only its first k entries (the device top-k)."""
     if k is not None and k <= TOPK_MAX and hasattr(model, "topk_users"):
-        users = np.flatnonzero(np.diff(test_csr.indptr) > 0)
-        for s in range(0, len(users), block):
-            ub = users[s:s + block]
+        for _, ub in _user_blocks(test_csr, block):
             top = model.topk_users(ub, int(k), train_csr)      # (len(ub), k) int64, host
             for r, u in enumerate(ub):
                 yield u, _row(test_csr, u), top[r]
@@ -72,8 +75,7 @@ def _topk_hits(model, test_csr, train_csr, k, block=4096):
     rows = np.repeat(np.arange(test_csr.shape[0], dtype=np.int64), np.diff(test_csr.indptr))
     keys = np.sort(rows * I + test_csr.indices.astype(np.int64))
     hits = np.empty((len(users), k), bool)
-    for s in range(0, len(users), block):
-        ub = users[s:s + block]
+    for s, ub in _user_blocks(test_csr, block):
         top = np.asarray(model.topk_users(ub, int(k), train_csr), dtype=np.int64)[:, :k]
         q = ub[:, None].astype(np.int64) * I + top
         pos = np.minimum(np.searchsorted(keys, q), len(keys) - 1)
@@ -103,8 +105,7 @@ def _mrr_from_ranks(model, test_csr, train_csr, block=4096):
     n_t = np.diff(test_csr.indptr)
     users = np.flatnonzero(n_t > 0)
     out = np.empty(len(users), dtype=np.float64)
-    for s in range(0, len(users), block):
-        ub = users[s:s + block]
+    for s, ub in _user_blocks(test_csr, block):
         n = n_t[ub]
         ranks = np.asarray(model.rank_users(ub, test_csr, train_csr), dtype=np.float64)
         out[s:s + len(ub)] = np.add.reduceat(1.0 / ranks, np.cumsum(n) - n) / n

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from recommendation_gans_amd import _lib
+from tests.ncf_infer_common import HostOnly
 
 pytestmark = pytest.mark.gpu
 
@@ -74,11 +75,6 @@ class _DeviceModel:
         return device_topk(sub.cpu(), k).astype(np.int64)
 
 
-class _HostOnly:
-    def __init__(self, m):
-        self.score_users = m.score_users
-
-
 def test_metrics_from_device_topk_match_host_ranking():
     from recommendation_gans_amd.spotlight import evaluation
     from recommendation_gans_amd.spotlight.interactions import Interactions
@@ -87,7 +83,7 @@ def test_metrics_from_device_topk_match_host_ranking():
     m = _DeviceModel(torch.rand(U, I, generator=torch.Generator().manual_seed(1)))
     test = Interactions(rs.randint(0, U, 3000), rs.randint(0, I, 3000), num_users=U, num_items=I)
     train = Interactions(rs.randint(0, U, 9000), rs.randint(0, I, 9000), num_users=U, num_items=I)
-    h = _HostOnly(m)
+    h = HostOnly(m)
     for k in (1, 5, 10):
         assert evaluation.precision_recall_score(m, test, k=k) == evaluation.precision_recall_score(h, test, k=k)
         assert evaluation.precision_recall_score(m, test, train, k=k) == \

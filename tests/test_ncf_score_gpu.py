@@ -21,79 +21,12 @@ import pytest
 import torch
 
 from recommendation_gans_amd import _lib
+from tests.ncf_infer_common import DEV, Device, HostOnly, forward64, make_model, random_params
 
 pytestmark = pytest.mark.gpu
 
 RTOL, ATOL = 1e-5, 1e-7
 TILE, GROUP = _lib.RG_NCF_SCORE_ITEM_TILE, _lib.RG_NCF_SCORE_USER_GROUP
-DEV = "cuda:0"
-
-
-def tower(E):
-    sizes = [2 * E]
-    while sizes[-1] > 8:
-        sizes.append(sizes[-1] // 2)
-    return sizes
-
-
-def random_params(E, M, U, I, seed):
-    """Reference-style init in named_parameters() order: N(0, 1) embeddings, Xavier-uniform weights,
-    small random biases."""
-    rs = np.random.RandomState(seed)
-    f = np.float32
-    p = [rs.randn(U, E).astype(f), rs.randn(I, E).astype(f)]
-    if M:
-        p += [rs.randn(U, M).astype(f), rs.randn(I, M).astype(f)]
-    sizes = tower(E)
-    shapes = [(o, i) for i, o in zip(sizes[:-1], sizes[1:])] + [(1, 8 + M)]
-    for o, i in shapes:
-        lim = np.sqrt(6.0 / (i + o))
-        p += [rs.uniform(-lim, lim, (o, i)).astype(f), rs.uniform(-0.1, 0.1, o).astype(f)]
-    return p
-
-
-def forward64(params, M, n_items=None):
-    """float64 eval-mode forward (mlp.py:30-41 / neuMF.py:34-55) of every (user, item) pair."""
-    p = [np.asarray(x, dtype=np.float64) for x in params]
-    uw, iw = p[0], p[1][:n_items]
-    mlp = p[4:] if M else p[2:]
-    U, I = len(uw), len(iw)
-    x = np.concatenate([np.repeat(uw[:, None, :], I, 1), np.repeat(iw[None, :, :], U, 0)], -1)
-    slope = float(np.float32(0.1))
-    for k in range(0, len(mlp) - 2, 2):
-        z = x @ mlp[k].T + mlp[k + 1]
-        x = np.where(z > 0, z, z * slope)
-    if M:
-        x = np.concatenate([x, p[2][:, None, :] * p[3][:n_items][None, :, :]], -1)
-    z = (x @ mlp[-2].T + mlp[-1])[..., 0]
-    return 1.0 / (1.0 + np.exp(-z))
-
-
-class Device:
-    """The model's tensors on the device and its rg_ncf_model_t (moments null: the model is read-only)."""
-
-    def __init__(self, params, E, M, n_items=None):
-        t = [torch.from_numpy(np.ascontiguousarray(x)).to(DEV) for x in params]
-        self.uw, self.iw = t[0], t[1][:n_items].contiguous()
-        self.mf = [t[2], t[3][:n_items].contiguous()] if M else [None, None]
-        self.mlp = torch.cat([x.reshape(-1) for x in (t[4:] if M else t[2:])]).contiguous()
-        self.U, self.I, self.E, self.M = self.uw.shape[0], self.iw.shape[0], E, M
-        self.model = _lib.NCFModel(_lib.ptr(self.uw), _lib.ptr(self.iw), None, None, None, None, _lib.ptr(self.mlp),
-                                   None, None, self.U, self.I, E, M)
-        self.model.mf_user_w, self.model.mf_item_w = _lib.ptr(self.mf[0]), _lib.ptr(self.mf[1])
-
-    def score(self, users, ld=None, sentinel=-7.0):
-        lib = _lib.load()
-        n, ld = len(users), self.I if ld is None else ld
-        u = torch.as_tensor(np.asarray(users, dtype=np.int64), device=DEV)
-        need = lib.rg_ncf_score_workspace_len(ctypes.byref(self.model), n)
-        assert need == (self.I + n) * self.E + n * ((self.M + 3) // 4 * 4)
-        ws = torch.empty(max(need, 1), dtype=torch.float32, device=DEV)
-        out = torch.full((n, ld), sentinel, dtype=torch.float32, device=DEV)
-        _lib.check(lib.rg_ncf_score_users(_lib.stream_handle(), ctypes.byref(self.model), _lib.ptr(u), n, _lib.ptr(ws),
-                                          _lib.ptr(out), ld), "rg_ncf_score_users")
-        torch.cuda.synchronize()
-        return out.cpu().numpy()
 
 
 GOLDEN_CASES = ["mlp_e64", "mlp_e16", "neumf_e16_m50", "neumf_e8_m5"]
@@ -188,40 +121,10 @@ def test_bad_arguments_fail_loudly():
 
 
 # ---------------------------------------------------------------- through the model
-def make_model(kind, tmp_path, monkeypatch):
-    from recommendation_gans_amd.implicit import ImplicitFactorizationModel
-    from recommendation_gans_amd.spotlight.dnn_models.mlp import MLP
-    from recommendation_gans_amd.spotlight.dnn_models.neuMF import NeuMF
-    from recommendation_gans_amd.spotlight.interactions import Interactions
-    monkeypatch.chdir(tmp_path)
-    U, I, E, M = 75, 3 * TILE + 7, 16, 5
-    torch.manual_seed(11)
-    if kind == "ncf":
-        net = MLP(layers=tower(E), num_users=U, num_items=I, embedding_dim=E)
-    else:
-        net = NeuMF(tower(E), U, I, mf_embedding_dim=M, mlp_embedding_dim=E)
-    rs = np.random.RandomState(4)
-    train = Interactions(rs.randint(0, U, 600).astype(np.int32), rs.randint(0, I, 600).astype(np.int32),
-                         ratings=np.ones(600, np.float32), num_users=U, num_items=I)
-    test = Interactions(rs.randint(0, U, 300).astype(np.int32), rs.randint(0, I, 300).astype(np.int32),
-                        ratings=np.ones(300, np.float32), num_users=U, num_items=I)
-    pool = list(zip(rs.randint(0, U, 500).tolist(), rs.randint(0, I, 500).tolist()))
-    model = ImplicitFactorizationModel(loss="pointwise", embedding_dim=E, n_iter=1, batch_size=64, representation=net,
-                                       random_state=np.random.RandomState(0), neg_examples=pool,
-                                       num_negative_samples=3, use_cuda=True)
-    model._initialize(train)
-    return model, train, test
-
-
-class _HostOnly:
-    def __init__(self, m):
-        self.score_users = m.score_users
-
-
 @pytest.mark.parametrize("kind", ["ncf", "neumf"])
 def test_model_paths_use_the_kernel(kind, tmp_path, monkeypatch):
     from recommendation_gans_amd.spotlight import evaluation
-    model, train, test = make_model(kind, tmp_path, monkeypatch)
+    model, train, test = make_model(kind, tmp_path, monkeypatch, U=75, I=3 * TILE + 7, n_test=300)
     e, U, I = model._engine, model._num_users, model._num_items
     assert e.neumf == (kind == "neumf")
     users = np.array([7, 3, 70, 3, 0, 74, 12])
@@ -247,7 +150,7 @@ def test_model_paths_use_the_kernel(kind, tmp_path, monkeypatch):
     for r, u in enumerate(users):
         x[r, csr[u].indices] = -np.inf
     assert (got == np.argsort(-x, axis=1, kind="stable")[:, :k]).all()
-    h = _HostOnly(model)
+    h = HostOnly(model)
     for k in (1, 5):
         assert evaluation.precision_recall_score(model, test, k=k) == evaluation.precision_recall_score(h, test, k=k)
         assert evaluation.precision_recall_score(model, test, train, k=k) == \

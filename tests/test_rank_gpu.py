@@ -12,6 +12,7 @@ import scipy.stats as st
 import torch
 
 from recommendation_gans_amd import _lib
+from tests.ncf_infer_common import HostOnly, make_model
 
 pytestmark = pytest.mark.gpu
 
@@ -261,11 +262,6 @@ class _DeviceModel:
         return a + (q + 1.0) / 2.0
 
 
-class _HostOnly:
-    def __init__(self, m):
-        self.score_users = m.score_users
-
-
 def test_mrr_from_device_ranks_matches_host_ranking():
     from recommendation_gans_amd.spotlight import evaluation
     from recommendation_gans_amd.spotlight.interactions import Interactions
@@ -274,50 +270,11 @@ def test_mrr_from_device_ranks_matches_host_ranking():
     m = _DeviceModel(torch.rand(U, I, generator=torch.Generator().manual_seed(1)))
     test = Interactions(rs.randint(0, U, 3000), rs.randint(0, I, 3000), num_users=U, num_items=I)
     train = Interactions(rs.randint(0, U, 9000), rs.randint(0, I, 9000), num_users=U, num_items=I)
-    h = _HostOnly(m)
+    h = HostOnly(m)
     for tr in (None, train):
         got = evaluation.mrr_score(m, test, tr)
         np.testing.assert_allclose(got, evaluation.mrr_score(h, test, tr), rtol=1e-12, atol=0)
     assert m.calls == 2
-
-
-def tower(E):
-    sizes = [2 * E]
-    while sizes[-1] > 8:
-        sizes.append(sizes[-1] // 2)
-    return sizes
-
-
-def make_model(kind, tmp_path, monkeypatch):
-    from recommendation_gans_amd.implicit import ImplicitFactorizationModel
-    from recommendation_gans_amd.spotlight.dnn_models.mlp import MLP
-    from recommendation_gans_amd.spotlight.dnn_models.neuMF import NeuMF
-    from recommendation_gans_amd.spotlight.factorization.representations import BilinearNet
-    from recommendation_gans_amd.spotlight.interactions import Interactions
-    monkeypatch.chdir(tmp_path)
-    U, I, E, M = 50, 300, 16, 5
-    torch.manual_seed(11)
-    if kind == "mf":
-        net = BilinearNet(U, I, E)
-        with torch.no_grad():                  # spread the scores: the default init leaves them all near 0.5
-            net.user_embeddings.weight.normal_()
-            net.item_embeddings.weight.normal_()
-            net.item_biases.weight.normal_()
-    elif kind == "ncf":
-        net = MLP(layers=tower(E), num_users=U, num_items=I, embedding_dim=E)
-    else:
-        net = NeuMF(tower(E), U, I, mf_embedding_dim=M, mlp_embedding_dim=E)
-    rs = np.random.RandomState(4)
-    train = Interactions(rs.randint(0, U, 600).astype(np.int32), rs.randint(0, I, 600).astype(np.int32),
-                         ratings=np.ones(600, np.float32), num_users=U, num_items=I)
-    test = Interactions(rs.randint(0, U - 3, 400).astype(np.int32), rs.randint(0, I, 400).astype(np.int32),
-                        ratings=np.ones(400, np.float32), num_users=U, num_items=I)
-    pool = list(zip(rs.randint(0, U, 500).tolist(), rs.randint(0, I, 500).tolist()))
-    model = ImplicitFactorizationModel(loss="pointwise", embedding_dim=E, n_iter=1, batch_size=64, representation=net,
-                                       random_state=np.random.RandomState(0), neg_examples=pool,
-                                       num_negative_samples=3, use_cuda=True)
-    model._initialize(train)
-    return model, train, test
 
 
 @pytest.mark.parametrize("kind", ["mf", "ncf", "neumf"])
@@ -325,7 +282,7 @@ def test_model_rank_users(kind, tmp_path, monkeypatch):
     """rank_users of a real model equals the ranks computed on the host from the model's own
     score block of the same users (exactly), and mrr_score takes it."""
     from recommendation_gans_amd.spotlight import evaluation
-    model, train, test = make_model(kind, tmp_path, monkeypatch)
+    model, train, test = make_model(kind, tmp_path, monkeypatch, U=50, I=300, n_test=400, test_users=47)
     users = np.array([7, 3, 49, 3, 0, 48, 12, 30])         # a repeat, and users 48 / 49 without test items
     tcsr, xcsr = test.tocsr(), train.tocsr()
     block = model.score_users(users)
@@ -338,7 +295,7 @@ def test_model_rank_users(kind, tmp_path, monkeypatch):
         assert got.dtype == np.float64 and got.shape == (sum(len(t) for t in tgt),)
         assert (got == a + (q + 1.0) / 2.0).all()
     assert model.rank_users(np.array([48, 49]), tcsr, xcsr).shape == (0,)
-    h = _HostOnly(model)
+    h = HostOnly(model)
     for tr in (None, train):
         np.testing.assert_allclose(evaluation.mrr_score(model, test, tr), evaluation.mrr_score(h, test, tr),
                                    rtol=1e-12, atol=0)
