@@ -23,22 +23,21 @@
 // consumers that ran ahead).  Events between streams are recorded lazily, when a
 // different stream has to be ordered after a production or a consumer.
 //
-// Overlapped step (RG_FUSED=1; pointwise / bpr / hinge; measured slower):
-//   main  rg_mf_step_front(pairs of t | marked prepare of t+1 | cold-row update of t)
-//         -> rg_mf_step_hot(touched rows of t, loss)
-// Two launches per step on one stream and no per-step event: the prepare of the
-// next step rides in the front grid, so the only cross-stream dependency left is
-// one wait per ring slot for the generated words.
-//
-// Split step (the default; adaptive hinge always):
+// Split step (the product's single-GPU step):
 //   main  rg_mf_pairs -> rg_mf_apply_prepare (dense update + the NEXT step's prepare in
 //         one launch) (-> exchange): no side stream, no per-step event
 // External consumers (validation, NCF, the Python split DP steps) go through
 // acquire / release, which prepare on a side stream ordered after the caller's work.
 //
 // Device memory: the caller (PyTorch) owns tables, scratch, pool and pairs; the
-// stepper owns its word ring, the per-slot start states, the row stamps of the
-// overlapped step and (jump path) the jump tables.
+// stepper owns its word ring, the per-slot start states and (jump path) the jump tables.
+//
+// This file: the word ring and generator, the prepare / prefetch machinery, the split step
+// (train_split), the data-parallel and owner-sharded steps, create / destroy and the dispatch
+// in rg_mf_stepper_train.  The Stepper struct and the helpers shared with the other half are in
+// rg_stepper.h.  The whole-step alternatives of the A/B build (overlapped RG_FUSED, lazy
+// RG_LAZY, pipelined RG_PIPE / RG_PIPE2; measured slower) are in
+// rg_stepper_alt.cpp with their buffers and their own C entries.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -49,133 +48,15 @@
 
 #include "rg_common.h"
 #include "rg_owner.h"
-
-#ifndef RG_PIPE_DEFAULT
-#define RG_PIPE_DEFAULT 0
-#endif
+#include "rg_stepper.h"
 
 #ifndef RG_OWNER_USER_AFTER_DEFAULT
 #define RG_OWNER_USER_AFTER_DEFAULT 0
 #endif
-#ifndef RG_PIPE2_DEFAULT
-#define RG_PIPE2_DEFAULT 0
-#endif
-namespace {
 
-constexpr int kSlots = 3;        // word slots in the ring
-constexpr int kAheadSlots = 2;   // slots generated ahead of the one being consumed
-
-struct Stepper {
-    rg_mf_stepper_config_t cfg;
-    bool failed = false;          // a step stopped half applied (pipe2's cold launch refused): unusable
-    hipStream_t gen = nullptr, prep = nullptr;
-    int64_t W = 0;                        // words per unit
-    int64_t G = 1;                        // units per ring slot
-    uint32_t *words[kSlots] = {nullptr, nullptr, nullptr};
-    uint32_t *start_state[kSlots] = {nullptr, nullptr, nullptr};   // [625] state before the slot
-    hipEvent_t gen_done[kSlots] = {nullptr, nullptr, nullptr};
-    hipEvent_t consumed[kSlots] = {nullptr, nullptr, nullptr};     // after the slot's last consumer
-    // Who produced / has seen / last consumed each slot.  Events are recorded lazily,
-    // only when a DIFFERENT stream has to be ordered after that work (same-stream
-    // order is free): the single-GPU split step then issues no event at all.
-    // (a null hipStream_t is the legacy default stream, a real consumer: validity is tracked
-    // by flags, never by null handles)
-    hipStream_t prod[kSlots] = {nullptr, nullptr, nullptr};        // producing stream
-    bool gen_rec[kSlots] = {false, false, false};                  // gen_done recorded after the production
-    hipStream_t seen[kSlots] = {nullptr, nullptr, nullptr};        // a stream ordered after the production
-    bool seen_ok[kSlots] = {false, false, false};
-    hipStream_t cons_on[kSlots] = {nullptr, nullptr, nullptr};     // stream of the last consumer
-    bool cons_ok[kSlots] = {false, false, false};                  // the slot was consumed since its production
-    bool cons_rec[kSlots] = {false, false, false};                 // consumed recorded after that consumer
-    bool inline_gen = false;              // split step: the walk of unit t+2 rides in step t's dense pass
-    hipEvent_t ready[2] = {nullptr, nullptr};                      // side-stream prepared pairs buffers
-    bool side_pending[2] = {false, false};                         // ready[b] not yet waited by the consumer
-    hipEvent_t mark = nullptr;                                     // consumer-stream point a side prepare follows
-    int64_t unit_base = 0;                // unit of relative slot 0 (reset when the state is loaded)
-    int64_t gen_slots = 0;                // relative slots generated
-    int64_t taken = 0;                    // units consumed
-    // prepared pairs of unit prep_unit for input prep_in, in pairs buffer prep_unit % 2
-    bool prepared = false;
-    int64_t prep_unit = -1;
-    rg_mf_step_in_t prep_in{};
-    int32_t prep_serial = 0;              // nonzero: prepared with row marks (stamp array prep_arr)
-    int prep_arr = 0;
-    int32_t serial = 0;                   // last mark serial issued
-    int32_t *stamp[2] = {nullptr, nullptr};   // [U + I] each, lazily allocated
-    int set = 0;                          // ping-pong set holding the current tables
-    bool fused = false;
-    bool hot_scan = true;
-    // MT jump-ahead path: the device state is in window form after a jump slot;
-    // cp_pos tracks CPython's position-in-block of the same stream point
-    rg::MtJumpPlan *jump = nullptr;
-    bool window_form = false;
-    int32_t cp_pos = 624;
-    bool win_at[kSlots] = {false, false, false};   // form / position at each slot's start
-    int32_t pos_at[kSlots] = {624, 624, 624};
-    // owner step over a communicator (dp_mode 2, world > 1; opt-in RG_OWNER_MT_SLICE=1 -- the
-    // emulated rank 0 of 8 measured 75.0 us per step with it, 74.6 without: the jump launches cost
-    // the same either way, and the slot's MT work already hides beside the step): each rank
-    // walks only ITS slice of every unit's words (L = W / world words at offset rank * L): a slot's
-    // G slices come from one head walk, one jump launch and G parallel segments, the device state
-    // ending G * W ahead; the slices are all-gathered on the generator stream
-    // (rg::comm_words_allgather), and gstate -- the global stream's state at the start of the next
-    // slot to produce, what the CPython state exports read -- is advanced by a jump of G * W per
-    // slot.  One rank's MT work per slot: G * L words walked G-wide and two jump launches, instead
-    // of the whole global draw's G * W words
-    bool slice = false;
-    int64_t L = 0;
-    rg::MtJumpPlan *slice_plan = nullptr, *gjump = nullptr, *rjump = nullptr;
-    uint32_t *gstate = nullptr, *jscratch = nullptr;
-    // owner-sharded step (dp_mode 2) between its parts
-    rg_mf_step_in_t own_in{};
-    int64_t own_unit = -1;
-    int own_stage = 0;                    // 0 idle, 1 after begin, 2 after mid
-    hipEvent_t own_back = nullptr;        // after the owner backward (the item gradient may start)
-    hipEvent_t own_grads = nullptr;       // train_owner: the lists are pulled (the user update may start)
-    hipEvent_t own_users = nullptr;       // train_owner: the user update is done (the next step may start)
-    // lazy dense pass (single-rank split step): deferred cold user-row updates
-    bool lazy = false;
-    bool lazy_pending = false;            // some user rows lag the current step
-    int64_t lazy_base = 0;                // absolute step of last_rel == 0
-    int32_t *last_rel = nullptr;          // [U]
-    int32_t *umark = nullptr;             // [U]
-    float *consts = nullptr;              // [2 * n_consts] Adam constants per absolute step
-    int64_t n_consts = 0;
-    uint64_t *rows_done = nullptr;        // diagnostic counter (rg_mf_stepper_lazy_count)
-    bool count_rows = false;
-    // claimed list slots (single-rank split step, rg_mf_work_t claim_num_users): the prepare of
-    // unit u claims in counts[u % 2] (cfg.work.row_count and a second array owned here), so the
-    // next unit's claims never meet the dense pass that reads and resets this unit's counts
-    bool claim = false;
-    int32_t *counts[2] = {nullptr, nullptr};
-    int32_t *own_counts = nullptr;
-    bool count_dirty[2] = {false, false};  // counts[b] hold claims no dense pass consumed yet
-    bool prep_claimed = false;             // the prepared pairs carry claimed slots
-    bool prep_in_pairs = false;            // split step: the next prepare rides in the pair pass
-    // pipelined step (rg_mf_pipe_step; single rank, claimed slots, pointwise / bpr / hinge):
-    // launch t updates step t's rows, runs step t+1's pair pass and step t+2's prepare.  A unit's
-    // scratch by its parity -- claims in pcounts[u % 3], lists / overflow accumulators / partials
-    // / planned partials in set u % 2 ([0] the caller's cfg.work, [1] owned here) -- and the
-    // users its pair pass reads in hot[u % 3] (length pint[u % 3]).
-    bool pipe = false;
-    int32_t *pcounts[3] = {nullptr, nullptr, nullptr};
-    int32_t *p_counts2 = nullptr;          // owned: pcounts[2]
-    bool pdirty[3] = {false, false, false};   // pcounts[k] hold claims no dense pass consumed
-    int32_t *p_list1 = nullptr;
-    int64_t *p_hg1 = nullptr, *p_hbg1 = nullptr;
-    float *p_part1 = nullptr, *p_prow1 = nullptr, *p_pbias1 = nullptr;
-    int32_t *hot[3] = {nullptr, nullptr, nullptr};
-    int32_t *pint = nullptr;               // [0..3) hot-list lengths, [3..5) gates, [5] error flag
-    bool pair_dirty[2] = {false, false};   // overflow accumulators of set k hold a pair pass's adds
-    int64_t paired = -1;                   // unit whose pair pass has run (its lists ready)
-    rg_mf_step_in_t paired_in{};
-    int64_t hot_prepped = -1;              // unit prepared with claims and a hot list, pair pending
-    rg_mf_step_in_t hot_in{};
-    int64_t last_pipe = -1;                // unit of the last pipelined launch (its counter resets)
-    // two-launch pipelined step (train_pipe2, the single-GPU default): the same per-unit scratch
-    // parities as `pipe`, no gate
-    bool pipe2 = false;
-};
+#pragma GCC visibility push(hidden)
+namespace rg {
+namespace stepper {
 
 int hip_fail(const char *what, hipError_t e) {
     rg::set_error(std::string(what) + ": " + hipGetErrorString(e));
@@ -406,32 +287,6 @@ int prepare_inline(Stepper &st, hipStream_t consumer, int64_t unit, const rg_mf_
     return RG_OK;
 }
 
-int ensure_stamps(Stepper &st) {
-    if (st.stamp[0]) return RG_OK;
-    const rg_mf_tables_t &t = st.cfg.tables[0];
-    const size_t bytes = (size_t)(t.num_users + t.num_items) * sizeof(int32_t);
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-        e = hipMalloc(&st.stamp[k], bytes);
-        if (e == hipSuccess) e = hipMemset(st.stamp[k], 0, bytes);
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    return e == hipSuccess ? RG_OK : hip_fail("stepper: stamps", e);
-}
-
-rg_mf_mark_t mark_of(const Stepper &st, int arr, int32_t serial) {
-    rg_mf_mark_t m{};
-    m.stamp = st.stamp[arr];
-    m.num_users = st.cfg.tables[0].num_users;
-    m.serial = serial;
-    return m;
-}
-
-int32_t next_serial(Stepper &st) {
-    st.serial = st.serial == 0x7fffffff ? 1 : st.serial + 1;
-    return st.serial;
-}
-
 // the consumer of `taken` has been enqueued on `stream`
 int release(Stepper &st, hipStream_t stream) {
     const int64_t rel = st.taken - st.unit_base;
@@ -446,11 +301,7 @@ int release(Stepper &st, hipStream_t stream) {
     return st.inline_gen ? RG_OK : keep_ahead(st, st.taken);
 }
 
-int lazy_flush(Stepper &st, hipStream_t s);
-
 // words + pairs of unit `taken` for `in`, visible to `stream` (split-step consumers)
-int pipe_abandon(Stepper &st, hipStream_t s);
-
 int acquire(Stepper &st, hipStream_t stream, const rg_mf_step_in_t &in, int64_t *unit_out) {
     const int64_t unit = st.taken;
     int rc = pipe_abandon(st, stream);    // a pipelined unit ahead is this consumer's now
@@ -499,56 +350,6 @@ rg_opt_t opt_at(const Stepper &st, int64_t t) {
         o.bias_correction2_sqrt = (float)std::pow(bc2, 0.5);
     }
     return o;
-}
-
-// Adam constants of every absolute step < upto on the device (grown by doubling; the
-// copy is synchronous and happens O(log steps) times in a run)
-int ensure_consts(Stepper &st, int64_t upto) {
-    if (upto < st.n_consts) return RG_OK;
-    int64_t cap = st.n_consts > 0 ? st.n_consts : 4096;
-    while (cap <= upto) cap *= 2;
-    float *host = static_cast<float *>(std::malloc((size_t)cap * 2 * sizeof(float)));
-    if (!host) { rg::set_error("stepper: out of host memory"); return RG_E_LAUNCH; }
-    for (int64_t s = 0; s < cap; ++s) {
-        const rg_opt_t o = opt_at(st, s > 0 ? s : 1);
-        host[2 * s] = o.step_size;
-        host[2 * s + 1] = o.bias_correction2_sqrt;
-    }
-    float *dev = nullptr;
-    hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMalloc(&dev, (size_t)cap * 2 * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(dev, host, (size_t)cap * 2 * sizeof(float), hipMemcpyHostToDevice);
-    std::free(host);
-    if (e != hipSuccess) return hip_fail("stepper: step constants", e);
-    if (st.consts) (void)hipFree(st.consts);
-    st.consts = dev;
-    st.n_consts = cap;
-    return RG_OK;
-}
-
-rg_mf_lazy_t lazy_of(const Stepper &st, int64_t step, bool full) {
-    rg_mf_lazy_t l{};
-    l.last_rel = st.last_rel;
-    l.umark = st.umark;
-    l.step_consts = st.consts;
-    l.n_consts = st.n_consts;
-    l.base = st.lazy_base;
-    l.step = step;
-    l.full = full ? 1 : 0;
-    l.rows_done = st.count_rows ? st.rows_done : nullptr;
-    return l;
-}
-
-// every user row up to the current step, into the current set (no-op when none lags)
-int lazy_flush(Stepper &st, hipStream_t s) {
-    if (!st.lazy || !st.lazy_pending) return RG_OK;
-    int rc = ensure_consts(st, st.cfg.step + 1);
-    if (rc) return rc;
-    const rg_opt_t o = opt_at(st, st.cfg.step > 0 ? st.cfg.step : 1);
-    const rg_mf_lazy_t l = lazy_of(st, st.cfg.step, true);
-    if ((rc = rg_mf_lazy_flush(s, &st.cfg.tables[st.set], &o, &l))) return rc;
-    st.lazy_pending = false;
-    return RG_OK;
 }
 
 bool env_flag(const char *name, bool dflt) {
@@ -677,370 +478,6 @@ int train_split(Stepper &st, hipStream_t s, const rg_mf_step_in_t &cur, const rg
         st.prep_serial = 0;
         st.prep_claimed = st.claim;
     }
-    st.set = 1 - st.set;
-    return RG_OK;
-}
-
-// ---------------------------------------------------------------- pipelined step
-rg_mf_work_t pipe_work(const Stepper &st, const rg_mf_step_in_t &in, int64_t unit) {
-    rg_mf_work_t w = work_for(st, in);
-    w.row_count = st.pcounts[unit % 3];
-    w.claim_num_users = st.cfg.tables[0].num_users;
-    if (unit % 2) {
-        w.row_list = st.p_list1;
-        w.hot_grad = st.p_hg1;
-        w.hot_bias_grad = st.p_hbg1;
-        w.loss_partials = st.p_part1;
-        w.part_row = st.p_prow1;
-        w.part_bias = st.p_pbias1;
-    }
-    return w;
-}
-
-int pipe_memset(void *p, size_t bytes, hipStream_t s, const char *what) {
-    hipError_t e = hipMemsetAsync(p, 0, bytes, s);
-    return e == hipSuccess ? RG_OK : hip_fail(what, e);
-}
-
-int pipe_clean_counts(Stepper &st, hipStream_t s, int k) {
-    if (!st.pdirty[k]) return RG_OK;
-    const rg_mf_tables_t &t = st.cfg.tables[0];
-    int rc = pipe_memset(st.pcounts[k], (size_t)(t.num_users + t.num_items) * sizeof(int32_t), s,
-                         "stepper: reset claims");
-    if (rc == RG_OK) st.pdirty[k] = false;
-    return rc;
-}
-
-// the overflow accumulators of set k after a pair pass whose dense pass never ran
-int pipe_clean_accum(Stepper &st, hipStream_t s, int k) {
-    if (!st.pair_dirty[k]) return RG_OK;
-    const rg_mf_tables_t &t = st.cfg.tables[0];
-    const int64_t rows = t.num_users + t.num_items;
-    int64_t *hg = k ? st.p_hg1 : reinterpret_cast<int64_t *>(st.cfg.work.hot_grad);
-    int64_t *hb = k ? st.p_hbg1 : reinterpret_cast<int64_t *>(st.cfg.work.hot_bias_grad);
-    int rc = pipe_memset(hg, (size_t)rows * t.dim * sizeof(int64_t), s, "stepper: reset overflow");
-    if (rc == RG_OK) rc = pipe_memset(hb, (size_t)rows * sizeof(int64_t), s, "stepper: reset overflow");
-    if (rc == RG_OK) st.pair_dirty[k] = false;
-    return rc;
-}
-
-// drop every pipelined unit not trained yet (a pair pass and / or a prepare ahead): their
-// claims and overflow adds are cleared; their words stay (input independent)
-int pipe_abandon(Stepper &st, hipStream_t s) {
-    if (!st.pipe && !st.pipe2) return RG_OK;
-    int rc = RG_OK;
-    for (int k = 0; k < 3 && rc == RG_OK; ++k) rc = pipe_clean_counts(st, s, k);
-    for (int k = 0; k < 2 && rc == RG_OK; ++k) rc = pipe_clean_accum(st, s, k);
-    st.paired = -1;
-    st.hot_prepped = -1;
-    st.last_pipe = -1;
-    st.prepared = false;
-    st.count_dirty[0] = st.count_dirty[1] = false;
-    return rc;
-}
-
-// Pipelined step of unit t = taken (see rg_mf_pipe_step).  Cold start (no pair pass of t
-// pending): prepare t (claims), pair pass t, prepare t+1 with its hot list, each its own launch;
-// then, while `next` is known, one launch per step.  Without `next` the step is the plain dense
-// pass and the pipeline drains.
-int train_pipe(Stepper &st, hipStream_t s, const rg_mf_step_in_t &cur, const rg_mf_step_in_t *next,
-               const rg_mf_step_in_t *next2, float *loss_out, void *ev0, void *ev1) {
-    const int64_t unit = st.taken;
-    int rc = generate_upto(st, unit + (next2 ? 2 : next ? 1 : 0), 0);
-    if (rc) return rc;
-    const rg_mf_tables_t *tb = &st.cfg.tables[st.set];
-    const rg_mf_tables_t &t0 = st.cfg.tables[0];
-    rg_mf_work_t w = pipe_work(st, cur, unit);
-    const rg_mf_batch_t batch = make_batch(st, cur, unit);
-    if (!(st.paired == unit && same_input(st.paired_in, cur))) {
-        // cold start: whatever ran ahead belongs to another input
-        if ((rc = pipe_abandon(st, s))) return rc;
-        if ((rc = wait_side(st, s, (int)(unit % 2))) || (rc = wait_words(st, s, unit))) return rc;
-        if ((rc = rg_mf_prepare(s, &batch, &w))) return rc;
-        st.pdirty[unit % 3] = true;
-        if ((rc = rg_mf_pairs(s, tb, &batch, &w, 1))) return rc;
-        st.pair_dirty[unit % 2] = true;
-        st.paired = unit;
-        st.paired_in = cur;
-    }
-    st.cfg.step += 1;
-    const rg_opt_t o = opt_at(st, st.cfg.step);
-    const rg_mf_loss_t l = loss_of(st, cur.global_pos, loss_out);
-    if (!next) {                       // the last step of a sequence: dense pass only
-        if ((rc = release(st, s))) return rc;
-        rg::launch_events() = rg::LaunchEvents{(hipEvent_t)ev0, (hipEvent_t)ev1};
-        rc = rg_mf_apply_prepare_gen(s, tb, &w, &o, 0, t0.num_users + t0.num_items, &l, nullptr, nullptr, nullptr);
-        rg::launch_events() = rg::LaunchEvents{};
-        if (rc) return rc;
-        st.pdirty[unit % 3] = false;
-        st.pair_dirty[unit % 2] = false;
-        st.paired = -1;
-        st.last_pipe = -1;
-        st.set = 1 - st.set;
-        return RG_OK;
-    }
-    // step t+1: prepared with claims and its hot list (done by the previous launch, or now)
-    const int64_t u1 = unit + 1, u2 = unit + 2;
-    rg_mf_work_t w1 = pipe_work(st, *next, u1);
-    const rg_mf_batch_t b1 = make_batch(st, *next, u1);
-    int32_t *nhot = st.pint, *gate = st.pint + 3, *err = st.pint + 5;
-    if (!(st.hot_prepped == u1 && same_input(st.hot_in, *next))) {
-        if ((rc = pipe_clean_counts(st, s, (int)(u1 % 3)))) return rc;
-        if ((rc = pipe_clean_accum(st, s, (int)(u1 % 2)))) return rc;
-        if ((rc = wait_side(st, s, (int)(u1 % 2))) || (rc = wait_words(st, s, u1))) return rc;
-        if ((rc = pipe_memset(nhot + u1 % 3, sizeof(int32_t), s, "stepper: hot list"))) return rc;
-        if ((rc = rg_mf_prepare_hot(s, &b1, &w1, st.hot[u1 % 3], nhot + u1 % 3))) return rc;
-        st.pdirty[u1 % 3] = true;
-        st.hot_prepped = u1;
-        st.hot_in = *next;
-    }
-    if (st.last_pipe != unit - 1) {    // counters a previous launch of the sequence would have reset
-        if ((rc = pipe_memset(gate + unit % 2, sizeof(int32_t), s, "stepper: gate")) ||
-            (rc = pipe_memset(nhot + u2 % 3, sizeof(int32_t), s, "stepper: hot list")))
-            return rc;
-    }
-    rg_mf_batch_t b2{};
-    rg_mf_work_t w2{};
-    if (next2) {
-        if ((rc = pipe_clean_counts(st, s, (int)(u2 % 3)))) return rc;
-        if ((rc = wait_side(st, s, (int)(u2 % 2))) || (rc = wait_words(st, s, u2))) return rc;
-        b2 = make_batch(st, *next2, u2);
-        w2 = pipe_work(st, *next2, u2);
-    }
-    if ((rc = pipe_clean_accum(st, s, (int)(u1 % 2)))) return rc;   // set u1 % 2 is the pair pass's
-    if ((rc = release(st, s))) return rc;
-    rg_mt_gen_t gen{};
-    int gen_slot = -1;
-    if (st.inline_gen && st.gen_slots == rel_slot(st, unit + 3)) {
-        gen_slot = (int)(st.gen_slots % kSlots);
-        if ((rc = begin_production(st, s, gen_slot))) return rc;
-        gen.state = st.cfg.mt_state;
-        gen.out = st.words[gen_slot];
-        gen.state_before = st.start_state[gen_slot];
-        gen.nwords = st.G * st.W;
-    }
-    rg_mf_pipe_t pp{};
-    pp.hot_users = st.hot[u1 % 3];
-    pp.nhot = nhot + u1 % 3;
-    pp.counts_next = st.pcounts[u1 % 3];
-    pp.gate = gate + unit % 2;
-    pp.gate_next = gate + u1 % 2;
-    pp.nhot_free = nhot + unit % 3;
-    pp.hot_out = next2 ? st.hot[u2 % 3] : nullptr;
-    pp.nhot_out = next2 ? nhot + u2 % 3 : nullptr;
-    pp.err = err;
-    rg::launch_events() = rg::LaunchEvents{(hipEvent_t)ev0, (hipEvent_t)ev1};
-    rc = rg_mf_pipe_step(s, tb, &w, &o, &l, &b1, &w1, next2 ? &b2 : nullptr, next2 ? &w2 : nullptr, &pp,
-                         gen_slot >= 0 ? &gen : nullptr);
-    rg::launch_events() = rg::LaunchEvents{};
-    if (rc) return rc;
-    if (gen_slot >= 0) end_production(st, s, gen_slot);
-    st.pdirty[unit % 3] = false;                 // the dense pass consumed and reset its claims
-    st.pair_dirty[unit % 2] = false;             // and its overflow accumulators
-    st.pair_dirty[u1 % 2] = true;
-    st.paired = u1;
-    st.paired_in = *next;
-    if (next2) {
-        st.pdirty[u2 % 3] = true;
-        st.hot_prepped = u2;
-        st.hot_in = *next2;
-    } else {
-        st.hot_prepped = -1;
-    }
-    st.last_pipe = unit;
-    st.set = 1 - st.set;
-    return RG_OK;
-}
-
-// Two-launch pipelined step of unit t = taken (rg_mf_pipe2_hot / rg_mf_pipe2_cold):
-//   hot  (t): step t's dense update of every item row and of the users step t+1's pair pass reads
-//   cold (t): step t+1's pair pass | the MT walk | step t+2's prepare | step t's dense update of
-//             every other user
-// Preconditions carried from the previous call: step t's pair pass ran (its lists), step t+1 was
-// prepared with claims and its hot list.  A cold start (nothing pending, or pending for another
-// input) runs prepare t, pair pass t and prepare t+1 as launches of their own; without `next` the
-// step is the plain dense pass and the pipeline drains; without `next2` the cold launch prepares
-// nothing ahead (the next call prepares its t+1 on its own).
-int train_pipe2(Stepper &st, hipStream_t s, const rg_mf_step_in_t &cur, const rg_mf_step_in_t *next,
-                const rg_mf_step_in_t *next2, float *loss_out, void *ev0, void *ev1) {
-    const int64_t unit = st.taken;
-    int rc = st.inline_gen ? generate_upto(st, unit + (next2 ? 2 : next ? 1 : 0), 0) : keep_ahead(st, unit);
-    if (rc) return rc;
-    const rg_mf_tables_t *tb = &st.cfg.tables[st.set];
-    const rg_mf_tables_t &t0 = st.cfg.tables[0];
-    rg_mf_work_t w = pipe_work(st, cur, unit);
-    const rg_mf_batch_t batch = make_batch(st, cur, unit);
-    if (!(st.paired == unit && same_input(st.paired_in, cur))) {
-        // cold start: whatever ran ahead belongs to another input
-        if ((rc = pipe_abandon(st, s))) return rc;
-        if ((rc = wait_side(st, s, (int)(unit % 2))) || (rc = wait_words(st, s, unit))) return rc;
-        if ((rc = rg_mf_prepare(s, &batch, &w))) return rc;
-        st.pdirty[unit % 3] = true;
-        if ((rc = rg_mf_pairs(s, tb, &batch, &w, 1))) return rc;
-        st.pair_dirty[unit % 2] = true;
-        st.paired = unit;
-        st.paired_in = cur;
-    }
-    st.cfg.step += 1;
-    const rg_opt_t o = opt_at(st, st.cfg.step);
-    const rg_mf_loss_t l = loss_of(st, cur.global_pos, loss_out);
-    const int64_t U = t0.num_users, R = U + t0.num_items;
-    if (!next) {                       // the last step of a sequence: dense pass only
-        if ((rc = release(st, s))) return rc;
-        rg::launch_events() = rg::LaunchEvents{(hipEvent_t)ev0, (hipEvent_t)ev1};
-        rc = rg_mf_apply_prepare_gen(s, tb, &w, &o, 0, R, &l, nullptr, nullptr, nullptr);
-        rg::launch_events() = rg::LaunchEvents{};
-        if (rc) return rc;
-        st.pdirty[unit % 3] = false;
-        st.pair_dirty[unit % 2] = false;
-        st.paired = -1;
-        st.hot_prepped = -1;
-        st.set = 1 - st.set;
-        return RG_OK;
-    }
-    const int64_t u1 = unit + 1, u2 = unit + 2;
-    rg_mf_work_t w1 = pipe_work(st, *next, u1);
-    const rg_mf_batch_t b1 = make_batch(st, *next, u1);
-    int32_t *nhot = st.pint;
-    if (!(st.hot_prepped == u1 && same_input(st.hot_in, *next))) {
-        if ((rc = pipe_clean_counts(st, s, (int)(u1 % 3)))) return rc;
-        if ((rc = pipe_clean_accum(st, s, (int)(u1 % 2)))) return rc;
-        if ((rc = wait_side(st, s, (int)(u1 % 2))) || (rc = wait_words(st, s, u1))) return rc;
-        if ((rc = pipe_memset(nhot + u1 % 3, sizeof(int32_t), s, "stepper: hot list"))) return rc;
-        if ((rc = rg_mf_prepare_hot(s, &b1, &w1, st.hot[u1 % 3], nhot + u1 % 3))) return rc;
-        st.pdirty[u1 % 3] = true;
-        st.hot_prepped = u1;
-        st.hot_in = *next;
-    }
-    rg_mf_batch_t b2{};
-    rg_mf_work_t w2{};
-    if (next2) {
-        if ((rc = pipe_clean_counts(st, s, (int)(u2 % 3)))) return rc;
-        if ((rc = wait_side(st, s, (int)(u2 % 2))) || (rc = wait_words(st, s, u2))) return rc;
-        b2 = make_batch(st, *next2, u2);
-        w2 = pipe_work(st, *next2, u2);
-    }
-    if ((rc = pipe_clean_accum(st, s, (int)(u1 % 2)))) return rc;   // set u1 % 2 is the pair pass's
-    if ((rc = release(st, s))) return rc;
-    rg_mt_gen_t gen{};
-    int gen_slot = -1;
-    if (st.inline_gen && st.gen_slots == rel_slot(st, unit + 3)) {
-        gen_slot = (int)(st.gen_slots % kSlots);
-        if ((rc = begin_production(st, s, gen_slot))) return rc;
-        gen.state = st.cfg.mt_state;
-        gen.out = st.words[gen_slot];
-        gen.state_before = st.start_state[gen_slot];
-        gen.nwords = st.G * st.W;
-    }
-    const int64_t hot_cap = std::min<int64_t>(U, (int64_t)(1 + st.cfg.n_neg) * st.cfg.cols);
-    if ((rc = rg_mf_pipe2_hot(s, tb, &w, &o, &l, st.hot[u1 % 3], nhot + u1 % 3, hot_cap,
-                              next2 ? nhot + u2 % 3 : nullptr, nullptr))) {
-        st.cfg.step -= 1;                          // nothing of this step ran
-        return rc;
-    }
-    rg::launch_events() = rg::LaunchEvents{(hipEvent_t)ev0, (hipEvent_t)ev1};   // the cold launch
-    rc = rg_mf_pipe2_cold(s, tb, &w, &o, &b1, &w1, st.pcounts[u1 % 3], next2 ? &b2 : nullptr,
-                          next2 ? &w2 : nullptr, next2 ? st.hot[u2 % 3] : nullptr, next2 ? nhot + u2 % 3 : nullptr,
-                          gen_slot >= 0 ? &gen : nullptr);
-    rg::launch_events() = rg::LaunchEvents{};
-    if (rc) {
-        // the hot launch updated part of the rows: the step is half applied and cannot be resumed
-        st.failed = true;
-        return rc;
-    }
-    if (gen_slot >= 0) end_production(st, s, gen_slot);
-    st.pdirty[unit % 3] = false;                 // the two launches consumed and reset its claims
-    st.pair_dirty[unit % 2] = false;             // and its overflow accumulators
-    st.pair_dirty[u1 % 2] = true;
-    st.paired = u1;
-    st.paired_in = *next;
-    if (next2) {
-        st.pdirty[u2 % 3] = true;
-        st.hot_prepped = u2;
-        st.hot_in = *next2;
-    } else {
-        st.hot_prepped = -1;
-    }
-    st.set = 1 - st.set;
-    return RG_OK;
-}
-
-// Lazy split step (single rank):
-//   main  rg_mf_pairs_prepare (this step's pairs + the NEXT step's prepare, which marks the
-//         users that step reads) -> rg_mf_apply_lazy (items, and the users with a gradient
-//         or a mark; a full pass when no next step is known; + the inline MT walk)
-// Every row a kernel reads is current; rows nobody reads lag until rg_mf_stepper_flush /
-// the next full pass / an external consumer (acquire) catches them up.
-int train_lazy(Stepper &st, hipStream_t s, const rg_mf_step_in_t &cur, const rg_mf_step_in_t *next,
-               float *loss_out, void *ev0, void *ev1) {
-    const int64_t unit = st.taken;
-    int rc = st.inline_gen ? generate_upto(st, unit + 1, 0) : keep_ahead(st, unit);
-    if (rc) return rc;
-    rg_mf_work_t w = work_for(st, cur);
-    const rg_mf_batch_t batch = make_batch(st, cur, unit);
-    if ((rc = wait_side(st, s, (int)(unit % 2)))) return rc;
-    if (!(st.prepared && st.prep_unit == unit && same_input(st.prep_in, cur))) {
-        // the pairs were not prepared (with marks) by the previous lazy step: bring every row
-        // up to date first, so whatever this step reads is current
-        if ((rc = lazy_flush(st, s))) return rc;
-        if ((rc = wait_words(st, s, unit))) return rc;
-        if ((rc = rg_mf_prepare(s, &batch, &w))) return rc;
-        st.prepared = true;
-        st.prep_unit = unit;
-        st.prep_in = cur;
-        st.prep_serial = 0;
-    }
-    if (!st.lazy_pending) {                    // every row current at cfg.step: restart the clock
-        hipError_t e = hipMemsetAsync(st.last_rel, 0, (size_t)st.cfg.tables[0].num_users * sizeof(int32_t), s);
-        if (e != hipSuccess) return hip_fail("stepper: reset last_rel", e);
-        st.lazy_base = st.cfg.step;
-    }
-    if (st.cfg.loss == RG_LOSS_ADAPTIVE_HINGE && (rc = wait_words(st, s, unit))) return rc;
-    const int64_t t = st.cfg.step + 1;
-    if ((rc = ensure_consts(st, t + 1))) return rc;
-    rg_mf_batch_t nbatch{};
-    rg_mf_work_t nw{};
-    if (next) {
-        // only the slot holding unit + 1: this unit is not released yet, and keeping two
-        // slots ahead of unit + 1 could overwrite its words under the adaptive-max kernel
-        // (release() below keeps the ring ahead once the pair pass is enqueued)
-        if (!st.inline_gen && (rc = generate_upto(st, unit + 1, 0))) return rc;
-        if ((rc = wait_side(st, s, (int)((unit + 1) % 2)))) return rc;
-        if ((rc = wait_words(st, s, unit + 1))) return rc;
-        nbatch = make_batch(st, *next, unit + 1);
-        nw = work_for(st, *next);
-    }
-    const rg_mf_tables_t *tb = &st.cfg.tables[st.set];
-    if ((rc = rg_mf_pairs_prepare(s, tb, &batch, &w, next ? &nbatch : nullptr, next ? &nw : nullptr, st.umark,
-                                  (int32_t)(t + 1))))
-        return rc;
-    if ((rc = release(st, s))) return rc;
-    rg_mt_gen_t gen{};
-    int gen_slot = -1;
-    if (st.inline_gen && st.gen_slots == rel_slot(st, unit + 2)) {
-        gen_slot = (int)(st.gen_slots % kSlots);
-        if ((rc = begin_production(st, s, gen_slot))) return rc;
-        gen.state = st.cfg.mt_state;
-        gen.out = st.words[gen_slot];
-        gen.state_before = st.start_state[gen_slot];
-        gen.nwords = st.G * st.W;
-    }
-    st.cfg.step = t;
-    const rg_opt_t o = opt_at(st, t);
-    const rg_mf_loss_t l = loss_of(st, cur.global_pos, loss_out);
-    const rg_mf_lazy_t lz = lazy_of(st, t, next == nullptr);
-    rg::launch_events() = rg::LaunchEvents{(hipEvent_t)ev0, (hipEvent_t)ev1};
-    rc = rg_mf_apply_lazy(s, tb, &w, &o, &l, &lz, gen_slot >= 0 ? &gen : nullptr);
-    rg::launch_events() = rg::LaunchEvents{};
-    if (rc) return rc;
-    if (gen_slot >= 0) end_production(st, s, gen_slot);
-    if (next) {
-        st.prepared = true;
-        st.prep_unit = unit + 1;
-        st.prep_in = *next;
-        st.prep_serial = 0;
-    }
-    st.lazy_pending = next != nullptr;
     st.set = 1 - st.set;
     return RG_OK;
 }
@@ -1355,78 +792,6 @@ int train_owner(Stepper &st, hipStream_t s, const rg_mf_step_in_t &cur, const rg
     return RG_OK;
 }
 
-// the touched rows of the hot pass: a stamp scan (RG_HOT_SCAN=1, default) or the owner flags
-const rg_mf_mark_t *hot_mark(const Stepper &st, const rg_mf_mark_t &m) { return st.hot_scan ? &m : nullptr; }
-
-int train_fused(Stepper &st, hipStream_t s, const rg_mf_step_in_t &cur, const rg_mf_step_in_t *next,
-                float *loss_out, void *ev0, void *ev1) {
-    int rc = ensure_stamps(st);
-    if (rc) return rc;
-    const int64_t unit = st.taken;
-    if ((rc = keep_ahead(st, unit))) return rc;
-    rg_mf_work_t w = work_for(st, cur);
-    const rg_mf_batch_t batch = make_batch(st, cur, unit);
-    if (!(st.prepared && st.prep_unit == unit && st.prep_serial != 0 && same_input(st.prep_in, cur))) {
-        // first step, or the prefetched pairs were for another input: marked prepare here
-        if ((rc = wait_side(st, s, (int)(unit % 2)))) return rc;
-        if ((rc = wait_words(st, s, unit))) return rc;
-        st.prep_arr = 1 - st.prep_arr;
-        st.prep_serial = next_serial(st);
-        const rg_mf_mark_t m = mark_of(st, st.prep_arr, st.prep_serial);
-        if ((rc = rg_mf_prepare_marked(s, &batch, &w, &m))) return rc;
-        st.prepared = true;
-        st.prep_unit = unit;
-        st.prep_in = cur;
-    }
-    const rg_mf_mark_t cur_mark = mark_of(st, st.prep_arr, st.prep_serial);
-    const rg_mf_tables_t *tb = &st.cfg.tables[st.set];
-    const int64_t U = tb->num_users, R = tb->num_users + tb->num_items;
-    const int64_t cold_end = st.cfg.item_grad ? U : R;    // DP: items go through the exchange
-    st.cfg.step += 1;
-    const rg_opt_t o = opt_at(st, st.cfg.step);
-    const rg_mf_loss_t l = loss_of(st, cur.global_pos, loss_out);
-
-    rg_mf_batch_t nbatch{};
-    rg_mf_work_t nw{};
-    rg_mf_mark_t nmark{};
-    const int narr = 1 - st.prep_arr;
-    if (next) {
-        if ((rc = keep_ahead(st, unit + 1))) return rc;
-        if ((rc = wait_side(st, s, (int)((unit + 1) % 2)))) return rc;
-        if ((rc = wait_words(st, s, unit + 1))) return rc;
-        nbatch = make_batch(st, *next, unit + 1);
-        nw = work_for(st, *next);
-        nmark = mark_of(st, narr, next_serial(st));
-    }
-    if ((rc = record(ev0, s))) return rc;
-    if ((rc = rg_mf_step_front(s, tb, &batch, &w, &cur_mark, &o, 0, cold_end, next ? &nbatch : nullptr,
-                               next ? &nw : nullptr, next ? &nmark : nullptr)))
-        return rc;
-    if ((rc = release(st, s))) return rc;               // clears `prepared` for this unit
-    if (next) {
-        st.prepared = true;
-        st.prep_unit = unit + 1;
-        st.prep_in = *next;
-        st.prep_serial = nmark.serial;
-        st.prep_arr = narr;
-    }
-    if (st.cfg.item_grad) {
-        if ((rc = rg_mf_grads(s, tb, &w, st.cfg.item_grad, U, R, &l))) return rc;
-        if (st.cfg.comm && (rc = rg::comm_begin(st.cfg.comm, s, st.cfg.item_grad,
-                                                tb->num_items * (int64_t)(tb->dim + 1) + 1)))
-            return rc;
-        if ((rc = rg_mf_step_hot(s, tb, &batch, &w, hot_mark(st, cur_mark), &o, 0, U, nullptr))) return rc;
-        if ((rc = record(ev1, s))) return rc;
-        if (st.cfg.comm && (rc = rg::comm_end(st.cfg.comm, s))) return rc;
-        if ((rc = rg_mf_apply_dense(s, tb, st.cfg.item_grad, &o, U, R, loss_out))) return rc;
-    } else {
-        if ((rc = rg_mf_step_hot(s, tb, &batch, &w, hot_mark(st, cur_mark), &o, 0, R, &l))) return rc;
-        if ((rc = record(ev1, s))) return rc;
-    }
-    st.set = 1 - st.set;
-    return RG_OK;
-}
-
 void destroy(Stepper *st) {
     if (st->gen) hipStreamSynchronize(st->gen);
     if (st->prep) hipStreamSynchronize(st->prep);
@@ -1437,20 +802,11 @@ void destroy(Stepper *st) {
         if (st->words[i]) hipFree(st->words[i]);
         if (st->start_state[i]) hipFree(st->start_state[i]);
     }
-    for (int i = 0; i < 2; ++i) {
+    for (int i = 0; i < 2; ++i)
         if (st->ready[i]) hipEventDestroy(st->ready[i]);
-        if (st->stamp[i]) hipFree(st->stamp[i]);
-    }
     if (st->mark) hipEventDestroy(st->mark);
-    if (st->last_rel) hipFree(st->last_rel);
-    if (st->umark) hipFree(st->umark);
-    if (st->consts) hipFree(st->consts);
-    if (st->rows_done) hipFree(st->rows_done);
+    alt_destroy(*st);
     if (st->own_counts) hipFree(st->own_counts);
-    for (void *p : {(void *)st->p_counts2, (void *)st->p_list1, (void *)st->p_hg1, (void *)st->p_hbg1,
-                    (void *)st->p_part1, (void *)st->p_prow1, (void *)st->p_pbias1, (void *)st->hot[0],
-                    (void *)st->hot[1], (void *)st->hot[2], (void *)st->pint})
-        if (p) hipFree(p);
     if (st->own_back) hipEventDestroy(st->own_back);
     if (st->own_grads) hipEventDestroy(st->own_grads);
     if (st->own_users) hipEventDestroy(st->own_users);
@@ -1465,7 +821,11 @@ void destroy(Stepper *st) {
     delete st;
 }
 
-}  // namespace
+}  // namespace stepper
+}  // namespace rg
+#pragma GCC visibility pop
+
+using namespace rg::stepper;
 
 extern "C" void *rg_mf_stepper_create(const rg_mf_stepper_config_t *cfg) {
     if (!cfg) { rg::set_error("rg_mf_stepper_create: null config"); return nullptr; }
@@ -1556,22 +916,6 @@ extern "C" void *rg_mf_stepper_create(const rg_mf_stepper_config_t *cfg) {
     // lazy dense pass (opt-in, RG_LAZY=1): the single-rank split step.  Bit-exact with the
     // eager pass but measured slower on gfx950 (the catch-up is ALU-bound).
     st->lazy = ab_flag("RG_LAZY", false) && cfg->dp_mode == 0 && !cfg->item_grad && !st->fused;
-    if (st->lazy) {
-        const size_t ub = (size_t)cfg->tables[0].num_users * sizeof(int32_t);
-        e = hipMalloc(&st->last_rel, ub);
-        if (e == hipSuccess) e = hipMalloc(&st->umark, ub);
-        if (e == hipSuccess) e = hipMemset(st->umark, 0, ub);
-        if (e == hipSuccess) e = hipMemset(st->last_rel, 0, ub);
-        if (e == hipSuccess) e = hipMalloc(&st->rows_done, sizeof(uint64_t));
-        if (e == hipSuccess) e = hipMemset(st->rows_done, 0, sizeof(uint64_t));
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess) {
-            hip_fail("rg_mf_stepper_create: lazy state", e);
-            destroy(st);
-            return nullptr;
-        }
-        st->lazy_base = cfg->step;
-    }
     // claimed list slots: the single-rank eager split step (RG_MF_CLAIM=0: the pair pass
     // claims its slots with returning atomics, as before)
     const rg_mf_tables_t &t0 = cfg->tables[0];
@@ -1594,51 +938,11 @@ extern "C" void *rg_mf_stepper_create(const rg_mf_stepper_config_t *cfg) {
         st->counts[1] = st->own_counts;
     }
     st->prep_in_pairs = ab_flag("RG_PREP_IN_PAIRS", false);
-    // pipelined step (rg_mf_pipe_step): single rank, claimed slots, pointwise / bpr / hinge, a
-    // float4 row layout of >= 8 lanes (dim a multiple of 4, 32..256)
-    st->pipe = ab_flag("RG_PIPE", RG_PIPE_DEFAULT) && st->claim && cfg->dp_mode == 0 && !st->prep_in_pairs &&
-               (cfg->loss == RG_LOSS_POINTWISE || cfg->loss == RG_LOSS_BPR || cfg->loss == RG_LOSS_HINGE) &&
-               t0.dim % 4 == 0 && t0.dim >= 32 && t0.dim <= 256 && cfg->work.part_row && cfg->work.part_bias &&
-               cfg->work.loss_partials && cfg->n_partials > 0;
-    if (st->pipe) {
-        // the pair workgroups wait inside the launch: keep them at most half of what the chip
-        // holds (>= 4 workgroups per CU at the launch's register count), so the rows they wait
-        // for always have room to run whatever the dispatch order
-        const int64_t upb = rg_mf_plan_units_per_block(t0.dim);
-        st->pipe = upb > 0 && (cfg->cols + upb - 1) / upb <= 2 * (int64_t)rg::num_cus() &&
-                   std::max(t0.num_users, t0.num_items) * (int64_t)t0.dim * 4 < ((int64_t)1 << 31);
-    }
-    // two-launch pipelined step (rg_mf_pipe2_hot / _cold) for the single-rank losses with claimed
-    // slots: RG_PIPE2=1 selects it, RG_PIPE2_DEFAULT the build's default (0: the split step, which
-    // measures faster -- DESIGN §4.1)
-    st->pipe2 = !st->pipe && ab_flag("RG_PIPE2", RG_PIPE2_DEFAULT != 0) && st->claim && cfg->dp_mode == 0 && !st->prep_in_pairs &&
-                (cfg->loss == RG_LOSS_POINTWISE || cfg->loss == RG_LOSS_BPR || cfg->loss == RG_LOSS_HINGE) &&
-                cfg->work.part_row && cfg->work.part_bias && cfg->work.loss_partials && cfg->n_partials > 0;
-    if (st->pipe || st->pipe2) {
-        const int64_t rows = t0.num_users + t0.num_items;
-        const int64_t hot_len = std::min<int64_t>(t0.num_users, (int64_t)(1 + cfg->n_neg) * cfg->cols);
-        e = hipMalloc(&st->p_counts2, (size_t)rows * sizeof(int32_t));
-        if (e == hipSuccess) e = hipMemset(st->p_counts2, 0, (size_t)rows * sizeof(int32_t));
-        if (e == hipSuccess) e = hipMalloc(&st->p_list1, (size_t)rows * RG_MF_LIST_CAP * 2 * sizeof(int32_t));
-        if (e == hipSuccess) e = hipMalloc(&st->p_hg1, (size_t)rows * t0.dim * sizeof(int64_t));
-        if (e == hipSuccess) e = hipMemset(st->p_hg1, 0, (size_t)rows * t0.dim * sizeof(int64_t));
-        if (e == hipSuccess) e = hipMalloc(&st->p_hbg1, (size_t)rows * sizeof(int64_t));
-        if (e == hipSuccess) e = hipMemset(st->p_hbg1, 0, (size_t)rows * sizeof(int64_t));
-        if (e == hipSuccess) e = hipMalloc(&st->p_part1, (size_t)cfg->n_partials * 2 * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc(&st->p_prow1, (size_t)cfg->cols * t0.dim * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc(&st->p_pbias1, (size_t)cfg->cols * sizeof(float));
-        for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipMalloc(&st->hot[k], (size_t)hot_len * sizeof(int32_t));
-        if (e == hipSuccess) e = hipMalloc(&st->pint, 8 * sizeof(int32_t));
-        if (e == hipSuccess) e = hipMemset(st->pint, 0, 8 * sizeof(int32_t));
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess) {
-            hip_fail("rg_mf_stepper_create: pipelined step buffers", e);
-            destroy(st);
-            return nullptr;
-        }
-        st->pcounts[0] = st->counts[0];
-        st->pcounts[1] = st->counts[1];
-        st->pcounts[2] = st->p_counts2;
+    // the alternatives' buffers (rg_stepper_alt.cpp): the lazy state, or -- exclusive with it, as
+    // they need claimed slots -- the pipelined steps' second scratch set (sets st->pipe / pipe2)
+    if (alt_create(*st) != RG_OK) {
+        destroy(st);
+        return nullptr;
     }
     // the jump-ahead walk (parallel segments) by default when every rank walks the global
     // stream of a multi-rank step: R times the words of one GPU's step
@@ -1723,22 +1027,6 @@ extern "C" int rg_mf_stepper_train_ahead(void *h, void *stream, const rg_mf_step
     if (st->pipe2 && st->cfg.dp_mode == 0)
         return train_pipe2(*st, (hipStream_t)stream, *cur, next, next2, loss_out, ev_apply_begin, ev_apply_end);
     return rg_mf_stepper_train(h, stream, cur, next, loss_out, ev_apply_begin, ev_apply_end);
-}
-
-extern "C" int rg_mf_stepper_pipelined(void *h) {
-    Stepper *st = static_cast<Stepper *>(h);
-    if (!st) return rg::fail_arg("rg_mf_stepper_pipelined: null handle");
-    return st->pipe ? 1 : st->pipe2 ? 2 : 0;
-}
-
-extern "C" int rg_mf_stepper_pipe_error(void *h, int32_t *err_out) {
-    Stepper *st = static_cast<Stepper *>(h);
-    if (!st || !err_out) return rg::fail_arg("rg_mf_stepper_pipe_error: null argument");
-    *err_out = 0;
-    if (!st->pipe) return RG_OK;
-    hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(err_out, st->pint + 5, sizeof(int32_t), hipMemcpyDeviceToHost);
-    return e == hipSuccess ? RG_OK : hip_fail("rg_mf_stepper_pipe_error", e);
 }
 
 extern "C" int rg_mf_stepper_dp_begin(void *h, void *stream, const rg_mf_step_in_t *cur, const rg_mf_step_in_t *next,
@@ -1974,26 +1262,4 @@ extern "C" int rg_mf_stepper_sync_mt(void *h, uint32_t *host_state, int32_t dire
         if ((e = hipStreamSynchronize(st->gen)) != hipSuccess) return hip_fail("stepper: slice state", e);
     }
     return RG_OK;
-}
-
-extern "C" int rg_mf_stepper_flush(void *h, void *stream) {
-    Stepper *st = static_cast<Stepper *>(h);
-    if (!st) return rg::fail_arg("rg_mf_stepper_flush: null handle");
-    return lazy_flush(*st, (hipStream_t)stream);
-}
-
-extern "C" int rg_mf_stepper_lazy_count(void *h, int32_t enable, uint64_t *rows_out) {
-    Stepper *st = static_cast<Stepper *>(h);
-    if (!st) return rg::fail_arg("rg_mf_stepper_lazy_count: null handle");
-    if (rows_out) {
-        *rows_out = 0;
-        if (st->rows_done) {
-            hipError_t e = hipDeviceSynchronize();
-            if (e == hipSuccess) e = hipMemcpy(rows_out, st->rows_done, sizeof(uint64_t), hipMemcpyDeviceToHost);
-            if (e == hipSuccess) e = hipMemset(st->rows_done, 0, sizeof(uint64_t));
-            if (e != hipSuccess) return hip_fail("rg_mf_stepper_lazy_count", e);
-        }
-    }
-    st->count_rows = enable != 0 && st->rows_done != nullptr;
-    return st->lazy ? 1 : 0;
 }

@@ -1,5 +1,6 @@
 # GPU box: same-box A/B of dense-pass variants at d = 128 and d = 64 (variants built with
-# build.py --variant NAME --only rg_mf.hip -D...).  Usage: bash scripts/gpu_ab_dense_layouts.sh
+# build.py --variant NAME --only rg_mf.hip -D..., which compiles rg_mf.hip and rg_mf_alt.hip as one
+# unit).  Usage: bash scripts/gpu_ab_dense_layouts.sh
 set -o pipefail
 mkdir -p gpurun_out
 R=$GRAFT_REPO_ROOT

@@ -34,6 +34,14 @@ def test_library_exports_all_header_symbols():
     assert not missing, missing
 
 
+def test_build_lists_every_csrc_file():
+    """Every file under csrc/ is a build input: a source left out is not linked, and a header left
+    out lets up_to_date() keep a stale library after it changes."""
+    from recommendation_gans_amd import build
+    on_disk = sorted(os.listdir(build.CSRC))
+    assert on_disk == sorted(build.SOURCES + build.HEADERS)
+
+
 def test_python_binding_covers_header():
     from recommendation_gans_amd import _lib
     bound = {n for n, _, _ in _lib.SIGNATURES}
