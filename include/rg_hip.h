@@ -24,6 +24,9 @@
  *   rg_mf_apply_dense   gradient (data parallel; no reference counterpart)
  *   rg_mf_scores        BilinearNet.forward (eval / predict)
  *                                                          implicit.py:368, :412
+ *   rg_mf_score_users   BilinearNet.forward of a block of users against every item
+ *                       (the block the ranking metrics read)
+ *                                                          spotlight/evaluation.py:13-60, :115-213
  *   rg_loss_finalize    loss.item() of run_val_iteration    implicit.py:366-379
  *   rg_mf_stepper_*     the loop body of fit: one call per run_train_iteration
  *                                                          implicit.py:290-298, :347-364
@@ -883,6 +886,31 @@ int rg_ncf_score_users(void *stream, const rg_ncf_model_t *model, const int64_t 
 #define RG_NCF_SCORE_PAIR_TILE 128
 int rg_ncf_score_pairs(void *stream, const rg_ncf_model_t *model, const int64_t *users_dev, const int64_t *items_dev,
                        int64_t n, float *out_dev);
+
+/* ------------------------------------------------------------------------------
+ * MF inference (rg_mf_score.hip): BilinearNet.forward (representations.py:62-91) of a block
+ * of users against every item, the block the ranking metrics read --
+ *     out[r][c] = sigmoid((<user_w[users[r]], item_w[c]> + user_b[users[r]]) + item_b[c])
+ * for r < n_users, c < num_items (the bias order of rg_mf_scores), into out [n_users][ld]
+ * (device, fp32, ld >= num_items; columns [num_items, ld) and rows past n_users are not
+ * written).  One launch: a workgroup (4 waves) per tile of RG_MF_SCORE_ITEM_TILE items x
+ * group of RG_MF_SCORE_USER_GROUP users stages the rows in LDS in chunks of 64 columns
+ * (50,688 B whatever the dim) and runs the product on v_mfma_f32_16x16x4_f32; bias, sigmoid
+ * and one store per score follow in registers.  dim in [1, 256]; 16-byte loads when
+ * dim % 4 == 0 and both tables are 16-byte aligned, scalar loads into zero-padded rows
+ * otherwise.  Every score is ONE fp32 accumulator chain with k ascending (no split-K, no
+ * atomics): the same bits at any position of the block, in any block size, on any call.
+ * The tables are only read; users_dev [n_users] int64 ids are trusted to be in range.
+ * Non-zero status (rg_last_error names the reason, no HIP call made) on a null pointer,
+ * dim outside [1, 256], num_items < 1, ld < num_items, n_users < 0, or more than 2^24 - 1
+ * (item tile, user group) workgroups; n_users == 0: RG_OK, no launch.
+ * ---------------------------------------------------------------------------- */
+#define RG_MF_SCORE_ITEM_TILE 128
+#define RG_MF_SCORE_USER_GROUP 64
+int rg_mf_score_users(void *stream, const float *user_w, const float *item_w,
+                      const float *user_b, const float *item_b, int32_t dim,
+                      int64_t num_items, const int64_t *users_dev, int64_t n_users,
+                      float *out_dev, int64_t ld);
 
 /* ------------------------------------------------------------------------------
  * Evaluation top-k (rg_eval.hip): the first k entries of argsort(-scores) per row, as

@@ -44,6 +44,15 @@ list of pairs, and one training batch of ``--batch`` random pairs.  Device event
 alternating; min / median, the largest relative difference of the two results, and the kernel's
 time against max(flops at the fp32 MFMA peak, gathered bytes at the HBM peak).  One JSON line per
 model and size.
+
+    python -m recommendation_gans_amd.eval_time --metric mf_scores [--items 26744] [--reps 20]
+
+times the MF score block, ``mf_engine.score_users_block`` (rg_mf_score_users, one fused launch)
+against ``mf_engine.score_users_torch`` (the chain of torch ops it replaced: gather, library GEMM,
+two broadcast adds, sigmoid) on the same tables and ids: 256 and 4096 users x ``--items`` items at
+d in {32, 64, 128}.  Device events, the two paths alternating; min / median per path, their ratio,
+the largest relative difference of the two blocks, and the kernel's time against max(flops at the
+fp32 MFMA peak, output bytes at the HBM peak).  One JSON line per shape.
 """
 import argparse
 import contextlib
@@ -324,6 +333,52 @@ def main_pairs(args):
     return out
 
 
+def main_mf_scores(args):
+    """``--metric mf_scores``: the MF score block, mf_engine.score_users_block (rg_mf_score_users)
+    against mf_engine.score_users_torch (gather, library GEMM, two adds, sigmoid) on the same tables
+    and ids: 256 and 4096 users x ``--items`` items at d in {32, 64, 128}."""
+    from . import mf_engine
+    dev = torch.device("cuda:0")
+    U, I = 138493, args.items
+    out = []
+    for d in (32, 64, 128):
+        g = torch.Generator().manual_seed(d)
+        tabs = [(torch.randn(U, d, generator=g) / d ** 0.5).to(dev), (torch.randn(I, d, generator=g) / d ** 0.5).to(dev),
+                (0.1 * torch.randn(U, generator=g)).to(dev), (0.1 * torch.randn(I, generator=g)).to(dev)]
+        for n in (256, 4096):
+            users = torch.from_numpy(np.random.RandomState(n).randint(0, U, n)).to(dev)
+            # the launch alone (ids checked once, here), and the call as _device_scores makes it: the
+            # ids' bounds come down to the host first, which the device waits for
+            new = lambda: mf_engine.score_users_block(*tabs, users, checked=True)
+            full = lambda: mf_engine.score_users_block(*tabs, users)
+            old = lambda: mf_engine.score_users_torch(*tabs, users)
+            for _ in range(3):                               # warm-up: code objects, GEMM algorithms, allocator
+                a, b = full(), old()
+                new()
+            torch.cuda.synchronize()
+            rel = float(((a - b).abs() / b.abs()).max())
+            del a, b
+            t_new, t_full, t_old = [], [], []
+            for _ in range(args.reps):                       # alternate the paths
+                t_new += timed(new, 1)
+                t_full += timed(full, 1)
+                t_old += timed(old, 1)
+            flops, bytes_ = 2.0 * n * I * d, 4.0 * n * I     # the product; the block written once
+            bound = max(flops / PEAK_FP32_MFMA, bytes_ / PEAK_HBM)
+            r = {"metric": "mf_scores", "dim": d, "users": n, "items": I, "reps": args.reps,
+                 "kernel_ms": stats(t_new), "with_id_check_ms": stats(t_full), "torch_ms": stats(t_old),
+                 "speedup_min": min(t_old) / min(t_new), "speedup_median": float(np.median(t_old) / np.median(t_new)),
+                 "speedup_with_id_check_median": float(np.median(t_old) / np.median(t_full)),
+                 "max_rel_diff": rel, "gflop": flops / 1e9, "mbytes": bytes_ / 1e6, "bound_ms": bound * 1e3,
+                 "bound_by": "flops" if flops / PEAK_FP32_MFMA >= bytes_ / PEAK_HBM else "bytes",
+                 "frac_of_bound": bound / (min(t_new) * 1e-3)}
+            print(json.dumps(r), flush=True)
+            out.append(r)
+        del tabs
+        torch.cuda.empty_cache()
+    return out
+
+
 def main_scores(args):
     """The default mode: one block of ``--users`` users against every item, NCFEngine.score_users
     (rg_ncf_score_users) against the pairwise NCFEngine.scores_torch."""
@@ -371,7 +426,7 @@ def main_scores(args):
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--metric", choices=("scores", "mrr", "slates", "pairs"), default="scores")
+    ap.add_argument("--metric", choices=("scores", "mrr", "slates", "pairs", "mf_scores"), default="scores")
     ap.add_argument("--batch", type=int, default=8192)
     ap.add_argument("--users", type=int, default=None)
     ap.add_argument("--hist-len", type=int, default=128)
@@ -385,7 +440,8 @@ def main(argv=None):
         args.users = ML20M_USERS if slates else 256
     if args.reps is None:
         args.reps = 5 if slates or args.metric == "pairs" else 20
-    return {"scores": main_scores, "mrr": main_mrr, "slates": main_slates, "pairs": main_pairs}[args.metric](args)
+    return {"scores": main_scores, "mrr": main_mrr, "slates": main_slates, "pairs": main_pairs,
+            "mf_scores": main_mf_scores}[args.metric](args)
 
 
 if __name__ == "__main__":

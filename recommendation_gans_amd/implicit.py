@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from . import _mtstate
+from . import mf_engine
 from .mf_engine import MFEngine
 from .ncf_engine import NCFEngine
 from .spotlight.factorization.representations import BilinearNet
@@ -57,6 +58,16 @@ def _csr_rows(csr, rows):
     np.cumsum(n, out=ptr[1:])
     pos = np.arange(ptr[-1], dtype=np.int64) + np.repeat(lo - ptr[:-1], n)
     return ptr, csr.indices[pos].astype(np.int32)
+
+
+def _score_block(model, users):
+    """(ids as a host int64 array, their contiguous fp32 score block on the device): what the
+    device rankings (topk_users, rank_users) read.  A function, not a method: it reads only
+    ``_engine.device`` and ``_device_scores``, so the rankings also work bound to a stand-in
+    that holds just the tables (bench.eval_model)."""
+    ub = np.asarray(users, dtype=np.int64)
+    u = torch.as_tensor(ub, device=model._engine.device)
+    return ub, model._device_scores(u).to(torch.float32).contiguous()
 
 
 class ImplicitFactorizationModel:
@@ -366,19 +377,15 @@ class ImplicitFactorizationModel:
         return self._engine.scores(u, i).detach().cpu().numpy().flatten()
 
     def _device_scores(self, u):
-        """(len(u), num_items) fp32 scores on the device: one GEMM of the tables (MF), or
+        """(len(u), num_items) fp32 scores on the device: the fused MF block (rg_mf_score_users;
+        tables that are not contiguous float32 on a CUDA device keep the chain of torch ops), or
         the eval-mode MLP / NeuMF block of the fused all-item kernel (rg_ncf_score_users)."""
         if self._kind == "mf":
             U, I, ub, ib = self._tables()
+            if mf_engine.score_block_on_device(U, I, ub, ib):
+                return mf_engine.score_users_block(U, I, ub, ib, u)
             return torch.sigmoid(U[u] @ I.T + ub[u][:, None] + ib[None, :])
         return self._engine.score_users(u)
-
-    def _score_block(self, users):
-        """(ids as a host int64 array, their contiguous fp32 score block on the device): what the
-        device rankings (topk_users, rank_users) read."""
-        ub = np.asarray(users, dtype=np.int64)
-        u = torch.as_tensor(ub, device=self._engine.device)
-        return ub, self._device_scores(u).to(torch.float32).contiguous()
 
     def score_users(self, users):
         """Scores of every item for a block of users, (len(users), num_items) float32 on
@@ -393,7 +400,7 @@ class ImplicitFactorizationModel:
         (len(users), k) int64 on the host."""
         from . import _lib
         dev = self._engine.device
-        ub, s = self._score_block(users)
+        ub, s = _score_block(self, users)
         if exclude_csr is not None:
             sub = exclude_csr[ub]
             if sub.nnz:
@@ -419,7 +426,7 @@ class ImplicitFactorizationModel:
         t_ptr, t_idx = _csr_rows(targets_csr, np.asarray(users, dtype=np.int64))
         if not len(t_idx):
             return np.zeros(0, dtype=np.float64)
-        ub, s = self._score_block(users)
+        ub, s = _score_block(self, users)
         tp, ti = torch.as_tensor(t_ptr, device=dev), torch.as_tensor(t_idx, device=dev)
         ep = ei = None
         if exclude_csr is not None:

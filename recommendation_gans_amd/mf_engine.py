@@ -107,6 +107,47 @@ class DeviceSampler:
         self.state.copy_(_as_u32_tensor(mt_state, self.device))
 
 
+def score_users_torch(U, I, ub, ib, users):
+    """The (len(users), num_items) score block as a chain of torch ops (gather, one GEMM, two
+    broadcast adds, sigmoid): what the evaluation ran before rg_mf_score_users, what it still
+    runs for tables the kernel does not take, and the timing baseline of ``score_users_block``."""
+    return torch.sigmoid(U[users] @ I.T + ub[users][:, None] + ib[None, :])
+
+
+def score_block_on_device(U, I, ub, ib):
+    """True if ``score_users_block`` takes these tables: all four on one CUDA device, float32,
+    contiguous, a dim the kernel has."""
+    tabs = (U, I, ub, ib)
+    return all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == U.device
+               for t in tabs) and U.dim() == 2 and I.dim() == 2 and 1 <= U.shape[1] <= 256 and \
+        I.shape[1] == U.shape[1] and I.shape[0] >= 1 and ub.numel() == U.shape[0] and ib.numel() == I.shape[0]
+
+
+def score_users_block(U, I, ub, ib, users, checked=False):
+    """Scores of ``users`` against every item, (len(users), num_items) float32 on the tables'
+    device: sigmoid((<U[u], I[i]> + ub[u]) + ib[i]) in one fused launch (rg_mf_score_users: the
+    product on the fp32 MFMA, bias and sigmoid in registers, one store per score).  A (user, item)
+    score is the same bits wherever the user stands in the block.  The tables (float32, contiguous,
+    on one CUDA device) are only read; an id outside [0, U.shape[0]) raises ValueError (one
+    download of the ids' bounds; ``checked=True``: the caller has checked these ids already)."""
+    if not score_block_on_device(U, I, ub, ib):
+        raise ValueError("score_users_block needs contiguous float32 tables of matching shapes on one CUDA device")
+    dev = U.device
+    users = torch.as_tensor(users).to(dev, torch.int64).reshape(-1).contiguous()
+    n, num_items = int(users.numel()), int(I.shape[0])
+    out = torch.empty(n, num_items, dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    if not checked:
+        lo, hi = torch.stack(users.aminmax()).tolist()
+        if lo < 0 or hi >= U.shape[0]:
+            raise ValueError("user ids outside the user table")
+    with torch.cuda.device(dev):
+        check(_lib.load().rg_mf_score_users(_lib.stream_handle(), ptr(U), ptr(I), ptr(ub), ptr(ib), int(U.shape[1]),
+                                            num_items, ptr(users), n, ptr(out), num_items), "rg_mf_score_users")
+    return out
+
+
 MFPlan = namedtuple("MFPlan", "perm pos_slot item_slot_off n_planned", defaults=(None,))
 
 
