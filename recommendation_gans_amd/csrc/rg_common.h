@@ -421,148 +421,28 @@ struct RowLayoutV {
     }
 };
 
-// A row of an EVEN runtime D <= 2 * LPU * K floats over LPU lanes in float2 pairs: pair c of lane
-// `sub` holds floats (c * LPU + sub) * 2 and + 1 (rows 8-B aligned when D is even), masked past D.
-// The dense pass's layout for even dims that are not a power of two (NeuMF's GMF width 50): one
-// 8-B load per lane and pair instead of a dword per element (element-wise arithmetic, same bits).
-template <int LPU_, int K_>
-struct RowLayoutP {
-    static constexpr int LPU = LPU_;
-    static constexpr int EPL = 2 * K_;
-    static constexpr bool VEC = false;
-    static constexpr int UPW = kWave / LPU;
-    __device__ static __forceinline__ int elem(int sub, int e) { return ((e >> 1) * LPU + sub) * 2 + (e & 1); }
-    __device__ static __forceinline__ void load_strided(float (&v)[EPL], const float *__restrict__ base, int64_t row,
-                                                        int64_t stride, int D, int sub) {
-#pragma unroll
-        for (int c = 0; c < K_; ++c) {
-            const int f = (c * LPU + sub) * 2;
-            float2 t = make_float2(0.0f, 0.0f);
-            if (f < D) t = *reinterpret_cast<const float2 *>(base + row * stride + f);
-            v[2 * c] = t.x; v[2 * c + 1] = t.y;
-        }
-    }
-    __device__ static __forceinline__ void load(float (&v)[EPL], const float *__restrict__ base, int64_t row, int D,
-                                                int sub) {
-        load_strided(v, base, row, D, D, sub);
-    }
-    __device__ static __forceinline__ void load_nt(float (&v)[EPL], const float *__restrict__ base, int64_t row, int D,
-                                                   int sub) {
-        load(v, base, row, D, sub);
-    }
-    __device__ static __forceinline__ void load_sc1(float (&v)[EPL], const float *__restrict__ base, int64_t row,
-                                                    int D, int sub) {
-        load(v, base, row, D, sub);   // only the pipelined step (A/B build, d = 64) reads past L1
-    }
-    __device__ static __forceinline__ void store(float *__restrict__ base, int64_t row, int D, int sub,
-                                                 const float (&v)[EPL]) {
-#pragma unroll
-        for (int c = 0; c < K_; ++c) {
-            const int f = (c * LPU + sub) * 2;
-            if (f < D) *reinterpret_cast<float2 *>(base + row * (int64_t)D + f) = make_float2(v[2 * c], v[2 * c + 1]);
-        }
-    }
-    __device__ static __forceinline__ void store_nt(float *__restrict__ base, int64_t row, int D, int sub,
-                                                    const float (&v)[EPL]) {
-        store(base, row, D, sub, v);
-    }
-    __device__ static __forceinline__ void store_wt(float *__restrict__ base, int64_t row, int D, int sub,
-                                                    const float (&v)[EPL]) {
-        store(base, row, D, sub, v);  // only the pipelined step (A/B build, d = 64) writes through
-    }
-    __device__ static __forceinline__ void store1_wt(float *p, float v) {
-        __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __device__ static __forceinline__ float load1_sc1(const float *p) {
-        return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __device__ static __forceinline__ void zero(float (&v)[EPL]) {
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) v[e] = 0.0f;
-    }
-};
-
-// The dense pass's layout for a dim's pair-pass layout L (mf_back_kernel, single-GPU MF):
-// RG_BACK_V32 / _V64 / _V128 = lanes per row of a RowLayoutV for d = 32 / 64 / 128 (0: L itself).
-// Measured (round 5, profiles/r5/attr/): d = 64 on 8 lanes x 2 float4 (8 rows per wave) instead of
-// 16 lanes x 1 float4: 55.1 -> 51.2 us per dense pass; d = 128 on 16 lanes x 2 float4 instead of
-// 32 x 1: 111.7 -> 104.3 us -- twice the bytes in flight per wave at a similar occupancy.
-#ifndef RG_BACK_V64
-#define RG_BACK_V64 8
-#endif
-#ifndef RG_BACK_V128
-#define RG_BACK_V128 16
-#endif
-#ifndef RG_BACK_V16
-#define RG_BACK_V16 0   // d = 16 on 2 lanes x 2 float4 / 1 x 4: 28.4-30.5 / 33.2-33.5 vs 26.7-28.9 us in the NeuMF
-#endif                  // step (its tower's tables), not kept (profiles/r6/ncf/neumf_dense_layouts_r6.txt)
-#ifndef RG_BACK_P
-#define RG_BACK_P 0     // even dims 33..64 that are not 64 (NeuMF's GMF 50) on RowLayoutP<RG_BACK_P, 32 / RG_BACK_P>
-                        // (float2 pairs; lanes per row): 8 lanes measured slower in the NeuMF step, 47.7-47.8 vs
-                        // 45.8-46.2 us (profiles/r6/ncf/neumf_dense_layouts_r6.txt)
-#endif
-#ifndef RG_BACK_V32
-#define RG_BACK_V32 4   // d = 32 on 4 lanes x 2 float4 (16 rows per wave) instead of 8 x 1: dense pass
-#endif                  // 34.0-34.5 -> 31.5-32.0 us, 140.6-142.0 -> 146.5-146.8 M/s (profiles/r6/mf/attr_r6m_d32.txt)
+// The dense pass's layout for a dim's pair-pass layout L (mf_back_kernel, single-GPU MF): a
+// RowLayoutV on half the lanes per row with two float4 per lane for d = 32 / 64 / 128, L itself
+// for every other dim -- twice the bytes in flight per wave at a similar occupancy.
 template <class L>
 struct BackLayout {
     using type = L;
 };
-#if RG_BACK_V64
-template <>
-struct BackLayout<RowLayout<16, 4, true>> {
-    using type = RowLayoutV<RG_BACK_V64, 64 / (4 * RG_BACK_V64)>;
-};
-#endif
-#if RG_BACK_V128
-template <>
-struct BackLayout<RowLayout<32, 4, true>> {
-    using type = RowLayoutV<RG_BACK_V128, 128 / (4 * RG_BACK_V128)>;
-};
-#endif
-#if RG_BACK_V16
-template <>
-struct BackLayout<RowLayout<4, 4, true>> {
-    using type = RowLayoutV<RG_BACK_V16, 16 / (4 * RG_BACK_V16)>;
-};
-#endif
-#if RG_BACK_P
-template <>
-struct BackLayout<RowLayout<16, 4, false>> {
-    using type = RowLayoutP<RG_BACK_P, 32 / RG_BACK_P>;   // even D only: the caller checks (BackLaunchF)
-};
-#endif
-#if RG_BACK_V32
+// d = 32 on 4 lanes x 2 float4 instead of 8 x 1: 34.0-34.5 -> 31.5-32.0 us (profiles/r6/mf/attr_r6m_d32.txt)
 template <>
 struct BackLayout<RowLayout<8, 4, true>> {
-    using type = RowLayoutV<RG_BACK_V32, 32 / (4 * RG_BACK_V32)>;
+    using type = RowLayoutV<4, 2>;
 };
-#endif
-
-// The split step's pair pass on its own row layout (RG_PAIR_V64 / RG_PAIR_V128 lanes per row, 0:
-// the dispatch layout): timing experiments of fewer lanes per row in the latency-bound gather
-#ifndef RG_PAIR_V64
-#define RG_PAIR_V64 0
-#endif
-#ifndef RG_PAIR_V128
-#define RG_PAIR_V128 0
-#endif
-template <class L>
-struct PairLayout {
-    using type = L;
-};
-#if RG_PAIR_V64
+// d = 64 on 8 lanes x 2 float4 (8 rows per wave) instead of 16 x 1: 55.1 -> 51.2 us (profiles/r5/attr/)
 template <>
-struct PairLayout<RowLayout<16, 4, true>> {
-    using type = RowLayoutV<RG_PAIR_V64, 64 / (4 * RG_PAIR_V64)>;
+struct BackLayout<RowLayout<16, 4, true>> {
+    using type = RowLayoutV<8, 2>;
 };
-#endif
-#if RG_PAIR_V128
+// d = 128 on 16 lanes x 2 float4 (4 rows per wave) instead of 32 x 1: 111.7 -> 104.3 us (profiles/r5/attr/)
 template <>
-struct PairLayout<RowLayout<32, 4, true>> {
-    using type = RowLayoutV<RG_PAIR_V128, 128 / (4 * RG_PAIR_V128)>;
+struct BackLayout<RowLayout<32, 4, true>> {
+    using type = RowLayoutV<16, 2>;
 };
-#endif
 
 // Dispatch on dim: calls f.template operator()<Layout>() for the layout of `dim`.
 template <typename F>

@@ -152,14 +152,9 @@ __global__ __launch_bounds__(kBlock) void mf_apply_kernel(ApplyArgs a) {
 // (~0.47 ns/word, one workgroup) hides under the HBM-bound pass, so a single-GPU step
 // needs no generator stream and no cross-stream event.
 template <class L, int NT, bool SPEC = false, bool OWN = false, bool LAZY = false, bool LSPEC = false>
-#ifdef RG_BACK_WAVES
-#define RG_BACK_ATTR __attribute__((amdgpu_waves_per_eu(RG_BACK_WAVES, 8)))
-#else
-#define RG_BACK_ATTR
-#endif
-__global__ __launch_bounds__(kBlock) RG_BACK_ATTR void mf_back_kernel(ApplyArgs a, PairsArgs prep, int2 *prep_out,
-                                                        int64_t apply_blocks, MtGenArgs gen, BackGrid bg,
-                                                        OwnerArgs own, MlpUpdArgs upd) {
+__global__ __launch_bounds__(kBlock) void mf_back_kernel(ApplyArgs a, PairsArgs prep, int2 *prep_out,
+                                                         int64_t apply_blocks, MtGenArgs gen, BackGrid bg,
+                                                         OwnerArgs own, MlpUpdArgs upd) {
     static_assert(kBlock == kOwnSeg, "an owner prepare segment is one workgroup");
     static_assert(kBlock == kGenThreads, "the MT walk runs on one full workgroup");
     const int64_t B = blockIdx.x;
@@ -338,22 +333,21 @@ struct PartialsLenF {
     int64_t cols;
     int64_t *nb;
     template <class L>
-    int operator()() { *nb = pairs_blocks<typename PairLayout<L>::type>(cols); return 0; }
+    int operator()() { *nb = pairs_blocks<L>(cols); return 0; }
 };
 
 struct UnitsPerBlockF {
     int64_t *upb;
     template <class L>
-    int operator()() { *upb = kPairBlock / PairLayout<L>::type::LPU; return 0; }
+    int operator()() { *upb = kPairBlock / L::LPU; return 0; }
 };
 
 struct PairsLaunchF {
     PairsArgs *a;
     hipStream_t s;
     bool adaptive, backward;
-    template <class L0>
+    template <class L>
     int operator()() {
-        using L = typename PairLayout<L0>::type;
         if (a->n_neg <= 5) return run<L, 5>();
         return run<L, kNMax>();
     }
@@ -675,9 +669,6 @@ static int apply_common(void *stream, const rg_mf_tables_t *t, rg_mf_work_t *w, 
     return dispatch_dim(t->dim, f);
 }
 
-#ifndef RG_BACK_V_NCF
-#define RG_BACK_V_NCF 1
-#endif
 namespace {
 struct BackLaunchF {
     ApplyArgs *a;
@@ -694,11 +685,9 @@ struct BackLaunchF {
         using LB = typename BackLayout<L>::type;
         if constexpr (!std::is_same<LB, L>::value) {
             // the dense pass (MF single-GPU, an owner rank's user rows, the NCF tail's embedding
-            // tables pulling their per-example gradient rows) on its own row layout (RG_BACK_V64 /
-            // _V128); element-wise arithmetic, so the same bits as the dispatch layout
-            constexpr bool pairs = !LB::VEC;   // RowLayoutP: float2 pairs, even dims only
-            if (!lazy && (a->contrib == nullptr || RG_BACK_V_NCF) && (!pairs || a->dim % 2 == 0))
-                return run<LB, true>();
+            // tables pulling their per-example gradient rows) on its own row layout (BackLayout);
+            // element-wise arithmetic, so the same bits as the dispatch layout
+            if (!lazy) return run<LB, true>();
         }
         return run<L, false>();
     }
@@ -746,28 +735,8 @@ struct BackLaunchF {
                 hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, *a, *prep, prep_out, nb, gen, bg, oa, ua);
         };
         if constexpr (V) {
-#ifndef RG_BACK_NT   // timing experiments: store policy of the V-layout dense pass (apply_row's NT)
-#define RG_BACK_NT 0
-#endif
-#ifdef RG_BACK_PIPE   // timing experiments: the persistent software-pipelined dense kernel (mf_dense_kernel)
-            if (!own) {
-                int64_t db = (int64_t)num_cus() * RG_BACK_PIPE;
-                const int64_t groups = (rows + L::UPW - 1) / L::UPW;
-                const int64_t need = (groups + kBlock / kWave - 1) / (kBlock / kWave);
-                if (db > need) db = need;
-                BackGrid dg{prep_blocks, 0, 0, 1, 0};
-                dg.apply_start = (head + 7) / 8 * 8;
-                const dim3 dgrid((unsigned)(dg.apply_start + db));
-                if (e0 || e1)
-                    hipExtLaunchKernelGGL(mf_dense_kernel<L>, dgrid, dim3(kBlock), 0, s, e0, e1, 0, *a, *prep, prep_out, db,
-                                          gen, dg);
-                else
-                    hipLaunchKernelGGL(mf_dense_kernel<L>, dgrid, dim3(kBlock), 0, s, *a, *prep, prep_out, db, gen, dg);
-                return check_launch("rg_mf_apply_prepare");
-            }
-#endif
             if (own) go(mf_back_kernel<L, 0, true, true>);
-            else go(mf_back_kernel<L, RG_BACK_NT, true>);
+            else go(mf_back_kernel<L, 0, true>);
             return check_launch("rg_mf_apply_prepare");
         } else {
         if (own) {
@@ -832,14 +801,11 @@ extern "C" int rg_mf_apply_prepare_gen(void *stream, const rg_mf_tables_t *t, rg
                                        int64_t row_begin, int64_t row_end, const rg_mf_loss_t *loss,
                                        const rg_mf_batch_t *next, const rg_mf_work_t *next_w,
                                        const rg_mt_gen_t *gen) {
-    MtGenArgs g{};
-    if (gen && gen->nwords > 0) {
-        if (!gen->state || !gen->out) return fail_arg("rg_mf_apply_prepare_gen: null MT state / output");
-        g.state = gen->state; g.out = gen->out; g.state_before = gen->state_before; g.nwords = gen->nwords;
-    }
-    ApplyArgs a;
-    int rc = apply_args(t, w, nullptr, nullptr, opt, row_begin, row_end, loss, nullptr, kApplyPull, a);
+    MtGenArgs g;
+    int rc = gen_args(gen, g, "rg_mf_apply_prepare_gen");
     if (rc) return rc;
+    ApplyArgs a;
+    if ((rc = apply_args(t, w, nullptr, nullptr, opt, row_begin, row_end, loss, nullptr, kApplyPull, a))) return rc;
     PairsArgs prep{};
     int64_t prep_blocks = 0;
     int2 *prep_out = nullptr;

@@ -335,9 +335,6 @@ __global__ __launch_bounds__(kBlock) void mf_pipe_kernel(ApplyArgs a, PairsArgs 
             cold = blk;
         } else if (blk < pp.cold1_blocks + pp.pair_blocks) {     // pair pass of step t + 1
         const int64_t pb = blk - pp.cold1_blocks;
-#ifdef RG_PIPE_X   // timing experiments only (wrong results): bit 0 no pair pass, bit 1 no wait either
-        if (RG_PIPE_X & 2) return;
-#endif
         if (threadIdx.x == 0) {
             const int target = (int)(pp.item_blocks + pp.huser_blocks);
             uint32_t spins = 0;
@@ -350,9 +347,6 @@ __global__ __launch_bounds__(kBlock) void mf_pipe_kernel(ApplyArgs a, PairsArgs 
             }
         }
         __syncthreads();
-#ifdef RG_PIPE_X
-        if (RG_PIPE_X & 1) return;
-#endif
         pairs_body<L, kFused, NMAX, true>(pa, pb);
         return;
         } else {
@@ -574,14 +568,9 @@ __global__ __launch_bounds__(kBlock) void mf_pipe2_cold_kernel(ApplyArgs a, Pair
     const int sub = lane & (LPU - 1);
     const int64_t u = blk * ((kBlock / kWave) * UPW) + (threadIdx.x >> 6) * UPW + lane / LPU;
     if (u >= a.num_users) return;
-#ifdef RG_PIPE2_CHECK_FIRST   // timing experiments: the hot test as a round trip of its own
-    if (p.counts_next[u] > 0) return;
-    apply_row<LD, kApplyPull, 0, false, true>(a, u, sub);
-#else
     // a user with a claim of step t+1 was updated by the hot launch: its guard is loaded beside its
     // other loads (wasted bytes for it, but no round trip in front of every row)
     apply_row<LD, kApplyPull, 0, false, true, false, false, true>(a, u, sub);
-#endif
 }
 
 }  // namespace rg

@@ -19,15 +19,11 @@
 namespace rg {
 
 constexpr int kCap = RG_MF_LIST_CAP;
-#ifndef RG_MF_PULL_GROUP
-#define RG_MF_PULL_GROUP 4
-#endif
 constexpr int kNMax = RG_MF_MAX_NEG;
 constexpr int kBlock = 256;
-#ifndef RG_MF_PAIR_BLOCK
-#define RG_MF_PAIR_BLOCK 256
-#endif
-constexpr int kPairBlock = RG_MF_PAIR_BLOCK;   // threads of a pair-pass workgroup (the plan's block)
+constexpr int kPairBlock = 256;   // threads of a pair-pass workgroup (the plan's block)
+constexpr int kPullGroup = 4;     // list entries whose partner rows apply_row loads per round
+constexpr int kLeanPullGroup = 2; // the same for lean_finish (one entry per lane)
 
 // kFused: forward + loss + lists.  kLossOnly: forward + loss (validation).
 // Adaptive hinge needs the global max first: kAdaptFwd (scores + max),
@@ -555,9 +551,6 @@ struct ApplyArgs {
     const int32_t *guard;
 };
 
-#ifndef RG_MF_SORTED_PULL
-#define RG_MF_SORTED_PULL 1
-#endif
 // sort the first ne of kCap list entries ascending by (other, dz bits) -- an 8-input
 // sorting network (19 compare-exchanges, register only); entries past ne key as +inf
 __device__ __forceinline__ uint64_t ent_key(int2 e, bool valid) {
@@ -726,12 +719,6 @@ __device__ __forceinline__ void catch_up(const ApplyArgs &a, float2 cl, int wmax
     }
 }
 
-#ifndef RG_LEAN_PULL
-#define RG_LEAN_PULL 0
-#endif
-#ifndef RG_LEAN_PG
-#define RG_LEAN_PG 2
-#endif
 // Ascending sort of the 8 list entries held one per lane (lanes sub 0..7 of each LPU-lane row
 // group; sub >= 8 hold +inf keys and sort among themselves): a bitonic network over lane
 // XOR partners, 6 compare-exchange stages of 64-bit keys.  The result (entry e on lane e) is
@@ -800,7 +787,7 @@ __device__ __forceinline__ void lean_load(const ApplyArgs &a, const int64_t r, c
 template <class L, bool WT = false>
 __device__ __forceinline__ void lean_finish(const ApplyArgs &a, const int64_t r, const int sub, const bool valid,
                                             LeanRow<L> &x) {
-    constexpr int EPL = L::EPL, LPU = L::LPU, PG = RG_LEAN_PG;
+    constexpr int EPL = L::EPL, LPU = L::LPU, PG = kLeanPullGroup;
     static_assert(LPU >= kCap, "one list entry per lane");
     const int D = a.dim;
     const int t = r < a.num_users ? 0 : 1;
@@ -815,10 +802,7 @@ __device__ __forceinline__ void lean_finish(const ApplyArgs &a, const int64_t r,
     const int rowbase = lane & ~(LPU - 1);
     if (__any(c > 0)) {
         const int ne = c < kCap ? c : kCap;
-        uint64_t key = ent_key(x.ent, sub < ne);
-#if RG_MF_SORTED_PULL
-        key = lane_sort8<LPU>(key, sub);
-#endif
+        const uint64_t key = lane_sort8<LPU>(ent_key(x.ent, sub < ne), sub);
         const float *other = a.contrib ? a.contrib + t * D : a.w_in[t ^ 1];
         const int64_t ostride = a.contrib ? a.contrib_stride : (int64_t)D;
         const bool fixp = c > kCap;   // an overflowed row sums list and surplus in fixed point
@@ -917,22 +901,11 @@ __device__ __forceinline__ void lean_finish(const ApplyArgs &a, const int64_t r,
     }
 }
 
-template <class L>
-__device__ __forceinline__ void apply_row_lean(const ApplyArgs &a, const int64_t r, const int sub) {
-    LeanRow<L> x;
-    lean_load<L>(a, r, sub, true, x);
-    lean_finish<L>(a, r, sub, true, x);
-}
-
 template <class L, int MODE, int NT, bool COLD, bool SPEC = false, bool LAZY = false, bool LSPEC = false,
           bool GUARD = false>
 __device__ __forceinline__ void apply_row(const ApplyArgs &a, const int64_t r, const int sub,
                                           const LazyRow lzr = LazyRow{}) {
     constexpr int EPL = L::EPL;
-    if constexpr (RG_LEAN_PULL && MODE == kApplyPull && !LAZY && !COLD && NT == 0 && L::LPU >= kCap) {
-        apply_row_lean<L>(a, r, sub);
-        return;
-    }
     const int64_t rb = a.row_begin, nr = a.row_end - rb;
     const int D = a.dim;
     const int t = r < a.num_users ? 0 : 1;          // 0: user table, 1: item table
@@ -1066,19 +1039,17 @@ __device__ __forceinline__ void apply_row(const ApplyArgs &a, const int64_t r, c
             for (int e = 0; e < kCap; ++e)
                 ent[e] = e < ne ? ((LSPEC && lz) ? lspec[LSPEC ? e : 0]
                                    : (SPEC && !lz) ? spec[SPEC ? e : 0] : a.row_list[r * kCap + e]) : make_int2(0, 0);
-#if RG_MF_SORTED_PULL
             // the entries' slots were claimed by atomics in arrival order: sorted by (partner,
             // dz bits) the row sums them in an order independent of that timing, so a step
             // whose rows do not overflow is bit-reproducible run to run
             sort_entries(ent, ne);
-#endif
             // MF: the partner row of the other table; NCF: the stored gradient half
             const float *other = a.contrib ? a.contrib + t * D : a.w_in[t ^ 1];
             const int64_t ostride = a.contrib ? a.contrib_stride : (int64_t)D;
-            // partner rows in groups of PG list entries (RG_MF_PULL_GROUP; most touched rows have
+            // partner rows in groups of PG list entries (kPullGroup; most touched rows have
             // 1-2 entries): a later group's gathers issue only when some row of the wave needs them,
             // and the smaller register footprint raises occupancy
-            constexpr int PG = kOneTrip ? kCap : RG_MF_PULL_GROUP;
+            constexpr int PG = kOneTrip ? kCap : kPullGroup;
             // an overflowed row (c > kCap) sums list and surplus in fixed point (see fix_add)
             const bool fixp = c > kCap;
             long long gf[EPL];

@@ -2,7 +2,7 @@
 // implicit.py:347-364; layers [2E, E, ..., 8] -> 1 as ncf_spotlight.py:53-56).
 //
 // One workgroup (4 waves) walks tiles of kRows = 32 examples (the E = 64 MLP's wave kernel:
-// ncfw::kR = RG_NCF_WAVE_ROWS = 48 in the product build); a tile holds whole
+// one wave per tile of ncfw::kR = 48); a tile holds whole
 // columns (a positive and its n negatives, pairs prepared by rg_mf_prepare), so
 // pairwise losses are resolved inside the tile.  Everything of a tile lives in
 // LDS: the MLP parameters (loaded once per workgroup), the activations of every
@@ -774,10 +774,9 @@ __global__ __launch_bounds__(256) void ncf_adapt_dp_kernel(const float *scores, 
 }
 
 // ============================================================================================
-// E = 64 tower (C3, mf_dim = 0): one WAVE per tile of RG_NCF_WAVE_ROWS rows -- 48 in the product
-// build since round 5 (8 whole columns of 1 + 5 rows: 1,024 tiles at B = 8192, n = 5, one per wave
-// of the 256 x 4-wave grid), the forward one example block at a time; 32-row tiles (1,639 tiles,
-// two rounds) measured 73.3 against 64.0 us.
+// E = 64 tower (C3, mf_dim = 0): one WAVE per tile of ncfw::kR = 48 rows (8 whole columns of
+// 1 + 5 rows: 1,024 tiles at B = 8192, n = 5, one per wave of the 256 x 4-wave grid), the forward
+// one example block at a time; 32-row tiles (1,639 tiles, two rounds) measured 73.3 against 64.0 us.
 //
 // The tile kernel above keeps every activation in LDS and spreads a tile's MFMA tiles over 8
 // waves: ~12 workgroup barriers and an LDS -> MFMA -> LDS round trip per layer, 14 % of the
@@ -789,8 +788,8 @@ __global__ __launch_bounds__(256) void ncf_adapt_dp_kernel(const float *scores, 
 //     feature 16t + 4g + r from lane group g, so  Y_{k+1}^T = W_{k+1} Y_k^T  and
 //     dA_k^T = W_k^T delta_k^T  consume the previous result straight from registers (the A
 //     operand, a weight, is read from LDS in the same permuted k order).
-//   * the forward runs the three example blocks together; the backward one block at a time
-//     (a third of the deltas live), each weight-gradient accumulator still taking the tile's
+//   * the forward and the backward each run one example block at a time (a third of the
+//     activations / deltas live), each weight-gradient accumulator still taking the tile's
 //     examples in row order (block 0's k-steps, then block 1's, ...).
 //   * the weight gradients dW_k = sum_e delta_k[e] X_k[e]^T contract over EXAMPLES, which the
 //     T layout keeps on lanes; X_k and delta_k are staged into the wave's own LDS rows
@@ -805,26 +804,11 @@ __global__ __launch_bounds__(256) void ncf_adapt_dp_kernel(const float *scores, 
 // ============================================================================================
 namespace ncfw {
 constexpr int kWaves = 4, kThreads = 64 * kWaves;
-// The forward one 16-example block at a time (as the backward), so a 48-row tile -- 8 whole
+// The forward runs one 16-example block at a time (as the backward), so a 48-row tile -- 8 whole
 // columns of 1 + 5 rows, 1,024 tiles at B = 8192: one per wave slot, no second round -- fits the
-// registers (12 B of scratch; 80 B with the forward over all blocks at once).  Measured (round 5,
-// profiles/r5/ncf/ncf_fwd_r6a.txt): 73.3 us per launch with 32-row tiles (1,639 tiles: two rounds
-// on 1,024 slots), 64.0 with these; 0: every block's forward at once (32 rows: 73.2 us)
-#ifndef RG_NCF_EARLY_TILE
-#define RG_NCF_EARLY_TILE 0      // 1: the first tile begun before the weights' barrier (its loop-carried
-                                 // state costs 156 B of scratch: 67.7-68.3 vs 62.3-63.0 us per launch,
-                                 // same box, profiles/r6/ncf/ncf_early_tile_ab_r6l.txt)
-#endif
-#ifndef RG_NCF_FWD_ROLLED
-#define RG_NCF_FWD_ROLLED 0      // 1: the blockwise forward's block loop kept rolled (400 B of scratch)
-#endif
-#ifndef RG_NCF_FWD_BLOCKWISE
-#define RG_NCF_FWD_BLOCKWISE 1
-#endif
-#ifndef RG_NCF_WAVE_ROWS
-#define RG_NCF_WAVE_ROWS 48   // 32: two rounds of tiles at B = 8192, n = 5 (1,639 tiles on 1,024 slots)
-#endif
-constexpr int kR = RG_NCF_WAVE_ROWS, NB = kR / 16;   // 48 rows = 3 example blocks of 16 (n = 5: 8 whole columns)
+// registers (12 B of scratch).  The alternatives that were measured (32-row tiles, every block's
+// forward at once, an early first tile) are in DESIGN §9, "Retired build switches".
+constexpr int kR = 48, NB = kR / 16;   // 48 rows = 3 example blocks of 16 (n = 5: 8 whole columns)
 // weights in LDS (floats): W_k row-major [out][in + 4] (b128 rows land on distinct 16-B slots),
 // W4 and the output row padded to 16 rows of zeros, biases padded with zeros
 constexpr int S1 = 132, S2 = 68, S3 = 36, S4 = 20, SO = 20;
@@ -860,89 +844,6 @@ __device__ __forceinline__ int at(int row, int col) {
 // inside the wave needs
 __device__ __forceinline__ void wave_sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
 
-// Y^T (TO tiles) = W X^T: W [16 TO][16 TI] (row stride S), X^T T-layout (TI tiles)
-template <int TI, int TO>
-__device__ __forceinline__ void fwd(const v4f (&x)[TI][NB], v4f (&y)[TO][NB], const float *W, int S, int g, int m) {
-#pragma unroll
-    for (int t = 0; t < TO; ++t)
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) y[t][nb] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int ti = 0; ti < TI; ++ti) {
-        v4f a[TO];
-#pragma unroll
-        for (int t = 0; t < TO; ++t) a[t] = *reinterpret_cast<const v4f *>(W + (16 * t + m) * S + 16 * ti + 4 * g);
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int t = 0; t < TO; ++t)
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) y[t][nb] = mfma(a[t][r], x[ti][nb][r], y[t][nb]);
-    }
-}
-
-// dA^T (TI tiles) = W^T delta^T: W [16 TO][16 TI] row-major (stride S), delta^T T-layout (TO
-// tiles); W may point at a column block of a wider matrix (its first of TI column tiles)
-template <int TI, int TO>
-__device__ __forceinline__ void bwd(const v4f (&d)[TO][NB], v4f (&da)[TI][NB], const float *W, int S, int g, int x) {
-#pragma unroll
-    for (int t = 0; t < TI; ++t)
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) da[t][nb] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int to = 0; to < TO; ++to)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float a[TI];
-#pragma unroll
-            for (int ti = 0; ti < TI; ++ti) a[ti] = W[(16 * to + 4 * g + r) * S + 16 * ti + x];
-#pragma unroll
-            for (int ti = 0; ti < TI; ++ti)
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) da[ti][nb] = mfma(a[ti], d[to][nb][r], da[ti][nb]);
-        }
-}
-
-// dW[16 TOo][16 TIi] += sum_e D[e][o] X[e][i] over the tile's examples (staged rows), and this
-// lane's share of the bias gradient sum_e D[e][o]: the examples e = g (mod 4) of column 16 to + x,
-// summed in the same pass over the D operand (the four lane groups are added at the end)
-template <int TOo, int TIi, int SD, int SX>
-__device__ __forceinline__ void dw(v4f (&acc)[TOo][TIi], float (&bs)[TOo], const float *D, const float *X, int g,
-                                   int x) {
-#pragma unroll
-    for (int s = 0; s < kR / 4; ++s) {
-        float a[TOo], b[TIi];
-#pragma unroll
-        for (int to = 0; to < TOo; ++to) a[to] = D[at<SD>(4 * s + g, 16 * to + x)];
-#pragma unroll
-        for (int ti = 0; ti < TIi; ++ti) b[ti] = X[at<SX>(4 * s + g, 16 * ti + x)];
-#pragma unroll
-        for (int to = 0; to < TOo; ++to) {
-#pragma unroll
-            for (int ti = 0; ti < TIi; ++ti) acc[to][ti] = mfma(a[to], b[ti], acc[to][ti]);
-            bs[to] += a[to];
-        }
-    }
-}
-
-// staged rows -> T-layout tiles (the inverse of stage)
-template <int T, int RS>
-__device__ __forceinline__ void unstage(v4f (&y)[T][NB], const float *R, int g, int j) {
-#pragma unroll
-    for (int t = 0; t < T; ++t)
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) y[t][nb] = *reinterpret_cast<const v4f *>(R + at<RS>(nb * 16 + j, 16 * t + 4 * g));
-}
-
-// T-layout tiles -> staged rows [example][feature] (float4 per lane)
-template <int T, int RS>
-__device__ __forceinline__ void stage(const v4f (&y)[T][NB], float *R, int g, int j) {
-#pragma unroll
-    for (int t = 0; t < T; ++t)
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) *reinterpret_cast<v4f *>(R + at<RS>(nb * 16 + j, 16 * t + 4 * g)) = y[t][nb];
-}
-
 // torch's LeakyReLU(0.1) -> Dropout(0.5) multiplier from the kept bit and the sign of the
 // output (A = z m with m > 0 keeps the sign of z; a dropped unit's delta is 0)
 __device__ __forceinline__ float mult(float y, bool keep, bool training) {
@@ -950,8 +851,8 @@ __device__ __forceinline__ float mult(float y, bool keep, bool training) {
     return training ? (keep ? 2.0f * m1 : 0.0f) : m1;
 }
 
-// ---- one example block (16 examples, lane j = example 16 nb + j): the backward runs block by
-// block so a third of the tile's activations / deltas is live at a time ----
+// ---- one example block (16 examples, lane j = example 16 nb + j): the forward and the backward
+// run block by block so a third of the tile's activations / deltas is live at a time ----
 // dA^T (TI tiles) = W^T delta^T for one block
 template <int TI, int TO>
 __device__ __forceinline__ void bwd1(const v4f (&d)[TO], v4f (&da)[TI], const float *W, int S, int g, int x) {
@@ -1234,18 +1135,6 @@ __global__ __launch_bounds__(ncfw::kThreads) __attribute__((amdgpu_waves_per_eu(
 #pragma unroll
     for (int k = 0; k < PTT; ++k)
         if (tid + k * kThreads < kTail) sw[oW4 + tid + k * kThreads] = wvt[k];
-#if RG_NCF_EARLY_TILE
-    // the first tile's ids and its X0 gather issued before the weights' barrier (they touch only
-    // this wave's LDS rows and global memory): its latency overlaps the other waves' weight copy
-    int ru = -1, ri = -1, rps = -1, ue[NB], ie[NB], re[NB];
-    uint32_t ke[NB];
-    v4f x0[8][NB];
-    bool begun = false;
-    if (first < a.tiles) {
-        begin_tile(a.tc, ru, ri, rps, ue, ie, re, ke, x0);
-        begun = true;
-    }
-#endif
     __syncthreads();
     float warm = 0.0f;   // the next tile's embedding lines, touched during this tile's backward
     for (int64_t tile = first; tile < a.tiles; tile += waves_total) {
@@ -1254,15 +1143,10 @@ __global__ __launch_bounds__(ncfw::kThreads) __attribute__((amdgpu_waves_per_eu(
         const int tl_ = (int)((tile - first) / waves_total);
         (void)tl_;
         WS(0);
-#if RG_NCF_EARLY_TILE
-        if (!begun) begin_tile(tc, ru, ri, rps, ue, ie, re, ke, x0);
-        begun = false;
-#else
         int ru = -1, ri = -1, rps = -1, ue[NB], ie[NB], re[NB];
         uint32_t ke[NB];
         v4f x0[8][NB];
         begin_tile(tc, ru, ri, rps, ue, ie, re, ke, x0);
-#endif
         if (warm == 1.0e30f && a.n_pos < 0) a.scores[0] = warm;   // keeps the warm-up loads (never taken)
         WS(1);
         // dropout bits of every unit of the tile, computed while the gather is in flight
@@ -1319,28 +1203,9 @@ __global__ __launch_bounds__(ncfw::kThreads) __attribute__((amdgpu_waves_per_eu(
             if (rps < 0 && !(lane < tc && a.pos_slot != nullptr)) li = atomicAdd(a.row_count + a.num_users + ri, 1);
         }
         WS(2);
-        // ---- forward ----
+        // ---- forward, one 16-example block at a time (as the backward): one block's activations
+        // live at once, so a 48-row tile (three blocks) fits the registers of a 32-row one ----
         // bias, LeakyReLU(0.1), Dropout(0.5) as one multiplier per unit
-        auto activate = [&](auto &y, const float *b, uint64_t kw, int bit0) {
-            constexpr int T = sizeof(y) / sizeof(y[0]);
-            v4f bv[T];
-#pragma unroll
-            for (int t = 0; t < T; ++t) bv[t] = *reinterpret_cast<const v4f *>(b + 16 * t + 4 * g);
-#pragma unroll
-            for (int t = 0; t < T; ++t)
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float z = y[t][nb][r] + bv[t][r];
-                        const float m1 = z > 0.0f ? 1.0f : 0.1f;
-                        const float m = training ? (((kw >> (bit0 + kbit(t, nb, r))) & 1U) ? 2.0f * m1 : 0.0f) : m1;
-                        y[t][nb][r] = z * m;
-                    }
-        };
-#if RG_NCF_FWD_BLOCKWISE
-        // the forward one 16-example block at a time (as the backward): one block's activations
-        // live at once, so a 48-row tile (three blocks) fits the registers of a 32-row one
         auto activate1 = [&](auto &y, const float *b, uint64_t kw, int bit0, int nb) {
             constexpr int T = sizeof(y) / sizeof(y[0]);
             v4f bv[T];
@@ -1357,11 +1222,7 @@ __global__ __launch_bounds__(ncfw::kThreads) __attribute__((amdgpu_waves_per_eu(
                 }
         };
         const float bo = sw[oBo];
-#if RG_NCF_FWD_ROLLED
-#pragma unroll 1
-#else
 #pragma unroll
-#endif
         for (int nb = 0; nb < NB; ++nb) {
             const int row = nb * 16 + j;
             v4f xb[8], a1[4], a2[2], a3[1], a4[1], zb[1];
@@ -1391,41 +1252,6 @@ __global__ __launch_bounds__(ncfw::kThreads) __attribute__((amdgpu_waves_per_eu(
             }
         }
         WS(3);
-#else
-        v4f y1[4][NB], y2[2][NB], y3[1][NB], y4[1][NB];
-        fwd<8, 4>(x0, y1, W1s, S1, g, j);
-        WS(3);
-        activate(y1, sw + oB1, kb1, 0);
-        stage<4, R1S>(y1, R1, g, j);
-        fwd<4, 2>(y1, y2, W2s, S2, g, j);
-        activate(y2, sw + oB2, kb2, 0);
-        stage<2, R2S>(y2, R2, g, j);
-        fwd<2, 1>(y2, y3, W3s, S3, g, j);
-        activate(y3, sw + oB3, kb2, 24);
-        stage<1, R3S>(y3, R3, g, j);
-        fwd<1, 1>(y3, y4, W4s, S4, g, j);
-        activate(y4, sw + oB4, kb2, 36);
-        if (kBackward) {   // A_4 rows with a ones feature (8) for the output layer's bias gradient
-            v4f y4s[1][NB];
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) {
-                y4s[0][nb] = y4[0][nb];
-                if (g == 2) y4s[0][nb][0] = 1.0f;
-            }
-            stage<1, R4S>(y4s, R4, g, j);
-        }
-        v4f zo[1][NB];
-        fwd<1, 1>(y4, zo, Wos, SO, g, j);
-        if (g == 0) {
-            const float bo = sw[oBo];
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) {
-                const float p = sigmoidf_ref(zo[0][nb][0] + bo);
-                sP[nb * 16 + j] = p;
-                if (PHASE == kNcfScores) a.scores[tile * kR + nb * 16 + j] = ue[nb] >= 0 ? p : 0.0f;
-            }
-        }
-#endif
         // list entries of the claimed slots (the atomics have returned by now)
         if (kBackward && lane < kR) {
             const int64_t ex = tile * kR + lane;
@@ -1839,9 +1665,8 @@ static int64_t ncf_param_len(const rg_ncf_model_t *m) {
     return m->mf_dim == 0 ? ncf_mlp_len(m->dim) : rg_neumf_param_len(m->dim, m->mf_dim);
 }
 extern "C" int64_t rg_ncf_mask_units(int32_t dim) { return ncf_mask_units(dim); }
-// rows per tile: RG_NCF_WAVE_ROWS for the wave kernel (E = 64 MLP; 48 in the product build --
-// 8 columns of 1 + 5 rows, one tile per wave at B = 8192), 32 for the tile kernel (the other
-// towers, NeuMF)
+// rows per tile: 48 (ncfw::kR) for the wave kernel (E = 64 MLP: 8 columns of 1 + 5 rows, one
+// tile per wave at B = 8192), 32 for the tile kernel (the other towers, NeuMF)
 extern "C" int64_t rg_ncf_rows_per_tile(int32_t dim, int32_t mf_dim) {
     if (ncf_mlp_len(dim) < 0 || mf_dim < 0 || mf_dim > RG_NEUMF_MAX_MF_DIM) return -1;
     return ncf_use_wave(dim, mf_dim) ? ncfw::kR : kRows;

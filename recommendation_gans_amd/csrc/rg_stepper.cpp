@@ -50,10 +50,6 @@
 #include "rg_owner.h"
 #include "rg_stepper.h"
 
-#ifndef RG_OWNER_USER_AFTER_DEFAULT
-#define RG_OWNER_USER_AFTER_DEFAULT 0
-#endif
-
 #pragma GCC visibility push(hidden)
 namespace rg {
 namespace stepper {
@@ -756,7 +752,7 @@ int train_owner(Stepper &st, hipStream_t s, const rg_mf_step_in_t &cur, const rg
     // pull then has the GPU alone), 2 the item exchange's enqueue -- measured, emulated rank 0 of
     // 8: 74.0-74.7 / 85.5-85.7 / 88.6-92.0 us per step (profiles/r5/owner/emul_order_r5x.txt).
     // It is enqueued as soon as that point is: behind the host's later launches it starts late
-    static const int after = ab_int("RG_OWNER_USER_AFTER", RG_OWNER_USER_AFTER_DEFAULT);
+    static const int after = ab_int("RG_OWNER_USER_AFTER", 0);
     const rg_opt_t o = opt_at(st, st.cfg.step + 1);
     auto start_users = [&]() -> int {
         if (!side) return RG_OK;

@@ -19,13 +19,6 @@
 
 #include "rg_stepper.h"
 
-#ifndef RG_PIPE_DEFAULT
-#define RG_PIPE_DEFAULT 0
-#endif
-#ifndef RG_PIPE2_DEFAULT
-#define RG_PIPE2_DEFAULT 0
-#endif
-
 #pragma GCC visibility push(hidden)
 namespace rg {
 namespace stepper {
@@ -563,7 +556,7 @@ int alt_create(Stepper &st) {
     const rg_mf_tables_t &t0 = cfg->tables[0];
     // pipelined step (rg_mf_pipe_step): single rank, claimed slots, pointwise / bpr / hinge, a
     // float4 row layout of >= 8 lanes (dim a multiple of 4, 32..256)
-    st.pipe = ab_flag("RG_PIPE", RG_PIPE_DEFAULT) && st.claim && cfg->dp_mode == 0 && !st.prep_in_pairs &&
+    st.pipe = ab_flag("RG_PIPE", false) && st.claim && cfg->dp_mode == 0 && !st.prep_in_pairs &&
                (cfg->loss == RG_LOSS_POINTWISE || cfg->loss == RG_LOSS_BPR || cfg->loss == RG_LOSS_HINGE) &&
                t0.dim % 4 == 0 && t0.dim >= 32 && t0.dim <= 256 && cfg->work.part_row && cfg->work.part_bias &&
                cfg->work.loss_partials && cfg->n_partials > 0;
@@ -576,9 +569,8 @@ int alt_create(Stepper &st) {
                    std::max(t0.num_users, t0.num_items) * (int64_t)t0.dim * 4 < ((int64_t)1 << 31);
     }
     // two-launch pipelined step (rg_mf_pipe2_hot / _cold) for the single-rank losses with claimed
-    // slots: RG_PIPE2=1 selects it, RG_PIPE2_DEFAULT the build's default (0: the split step, which
-    // measures faster -- DESIGN §4.1)
-    st.pipe2 = !st.pipe && ab_flag("RG_PIPE2", RG_PIPE2_DEFAULT != 0) && st.claim && cfg->dp_mode == 0 && !st.prep_in_pairs &&
+    // slots: RG_PIPE2=1 selects it; the default is the split step, which measures faster
+    st.pipe2 = !st.pipe && ab_flag("RG_PIPE2", false) && st.claim && cfg->dp_mode == 0 && !st.prep_in_pairs &&
                 (cfg->loss == RG_LOSS_POINTWISE || cfg->loss == RG_LOSS_BPR || cfg->loss == RG_LOSS_HINGE) &&
                 cfg->work.part_row && cfg->work.part_bias && cfg->work.loss_partials && cfg->n_partials > 0;
     if (st.pipe || st.pipe2) {

@@ -6,7 +6,7 @@
 # kernel trace (average mf_back / mf_pairs / mf_prepare durations).
 # Usage: bash scripts/gpu_attr.sh TAG name[:ENV=VAL] ...   (base* = the product library; a variant
 # name's part before '+' names the library; BARGS=... in the ENV part: extra bench.py arguments,
-# e.g. v16:BARGS=--dim=128)
+# e.g. NAME:BARGS=--dim=128)
 set -o pipefail
 TAG=${1:-run}; shift
 mkdir -p gpurun_out

@@ -1,7 +1,7 @@
 # GPU box: same-box A/B of library variants (python -m recommendation_gans_amd.build --variant NAME -D...).
 # For each NAME (base = the product library): the MF / plan parity tests against that library,
 # the bench at 20/5 and 200/20, and a kernel-trace profile (per-kernel average durations).
-# Usage: bash scripts/gpu_lib_ab.sh TAG base pb512 ...     (tests skipped if NOTEST=1)
+# Usage: bash scripts/gpu_lib_ab.sh TAG base NAME ...     (tests skipped if NOTEST=1)
 set -o pipefail
 TAG=${1:-run}; shift
 mkdir -p gpurun_out

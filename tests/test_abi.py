@@ -129,14 +129,15 @@ def test_no_gpu_means_loud_failure():
 
 def test_ncf_launch_geometry():
     """Host-side shape functions (no GPU): the E = 64 MLP runs one wave per tile of
-    rg_ncf_rows_per_tile(64, 0) rows (48 = 8 whole columns of 1 + 5 rows in the product; 32 in a
-    -DRG_NCF_WAVE_ROWS=32 build), 4 waves per workgroup, at most 256 workgroups; the other towers
-    and NeuMF keep the tile kernel's 32-row tiles and workgroup-per-tile count (capped by LDS)."""
+    rg_ncf_rows_per_tile(64, 0) rows (48 = 8 whole columns of 1 + 5 rows; 32 only on the A/B
+    build's RG_NCF_TILE=1 path, the tile kernel), 4 waves per workgroup, at most 256 workgroups; the
+    other towers and NeuMF keep the tile kernel's 32-row tiles and workgroup-per-tile count (capped
+    by LDS)."""
     from recommendation_gans_amd import _lib
     L = _lib.load()
     wave = not (_lib.ab_build() and os.environ.get("RG_NCF_TILE") == "1")
     R = int(L.rg_ncf_rows_per_tile(64, 0))
-    assert R in ((32, 48) if wave else (32,))
+    assert R == (48 if wave else 32)
     assert L.rg_ncf_rows_per_tile(32, 0) == 32 and L.rg_ncf_rows_per_tile(16, 50) == 32
     tc = R // 6
     assert L.rg_ncf_cols_per_tile(5, 64, 0) == tc and L.rg_ncf_tiles(8192, 5, 64, 0) == -(-8192 // tc)
