@@ -397,8 +397,27 @@ __global__ __launch_bounds__(256) void d_loss_kernel(const float *__restrict__ d
     }
 }
 
+// db4 of the D step: the real rows' sum of dout plus the fake rows' sum, each pass its own
+// sum in the same order (as autograd accumulates the two D calls).  dout is -1/B on the real
+// rows and +1/B on the fake rows, so the two sums are exact negatives and the gradient is
+// exactly 0 at any B, as the reference's.  One sum over the 2B stacked rows leaves a rounding
+// residue unless 1/B is a power of two (B = 160: -1.5e-8), which RMSprop's g / (sqrt(v) + eps)
+// turns into a step of 1.3 lr on the output bias (up to 10 lr).
+__global__ __launch_bounds__(256) void d_b4_grad_kernel(const float *__restrict__ dout, int B,
+                                                        float *__restrict__ out) {
+    __shared__ float red[256];
+    const int t = threadIdx.x;
+    float sr = 0.0f, sf = 0.0f;
+    for (int r = t; r < B; r += 256) {
+        sr += dout[r];
+        sf += dout[B + r];
+    }
+    const float a = block_sum256(sr, red), b = block_sum256(sf, red);
+    if (t == 0) out[0] = a + b;
+}
+
 // backward of the last D layer, elementwise: dl3 = dout * w4 * LeakyReLU'(u3) * mult3
-// (dW4 / db4 are weighted column sums: colsum_kernel)
+// (dW4 is a weighted column sum: colsum_kernel)
 __global__ __launch_bounds__(256) void d_out_bwd_kernel(const float *__restrict__ u3, const float *__restrict__ q3,
                                                         const float *__restrict__ dout, int rows, int K,
                                                         const float *__restrict__ w4, float *__restrict__ dl3) {
@@ -848,7 +867,9 @@ int d_upper_backward(const Ctx &x, const rg_gan_model_t *mdl, int rows, float *d
                        x.f(x.w.q3), x.f(x.w.dout), rows, (int)m.H1, D + x.dof[RG_GAN_D_W4], x.f(x.w.dl3));
     if (dgrad) {
         colsum(x.st, x.f(x.w.h3), rows, m.H1, m.H1, x.f(x.w.dout), gslot(RG_GAN_D_W4));
-        colsum(x.st, nullptr, rows, 1, 1, x.f(x.w.dout), gslot(RG_GAN_D_B4));
+        // the D step's stacked rows: rows = 2B, real then fake
+        hipLaunchKernelGGL(d_b4_grad_kernel, dim3(1), dim3(256), 0, x.st, x.f(x.w.dout), rows / 2,
+                           gslot(RG_GAN_D_B4));
     }
     const int64_t in[2] = {m.H, m.H2}, out[2] = {m.H1, m.H};      // layer 3 then layer 2
     const int64_t wblk[2] = {RG_GAN_D_W3, RG_GAN_D_W2}, bblk[2] = {RG_GAN_D_B3, RG_GAN_D_B2};

@@ -2,7 +2,10 @@
 
 * the fp32 MFMA GEMM against a float64 product of the same fp32 operands, every
   operand layout, split-K, ragged edges and the tanh epilogue (tolerance: 2e-6 of
-  sum |a b| per element, the f32 fma-chain bound at these K);
+  sum |a b| per element, the f32 fma-chain bound at these K); with M/N-major operands also
+  the K a ragged batch gives the weight-gradient GEMMs (1, 5, 37, 131: below one K step, a
+  ragged K step, a ragged last split), store and fused-RMSprop forms, the operands allocated
+  32 rows past K and those rows NaN, so a leak through the K mask shows in the result;
 * the discriminator / generator iterations against the reference's own steps
   (tests/golden/gan_*.npz, recorded z and dropout masks fed in): D outputs, G(z),
   losses, BatchNorm running stats, inference slates, and every parameter after
@@ -10,7 +13,15 @@
   elements whose float64 gradient cancels to noise excepted);
 * generation through the fused argmax epilogue (heads wider than a column tile)
   against the eval-mode forward of the float64 restatement;
-* the device dropout / noise path trains and is reproducible."""
+* the device dropout / noise path trains and is reproducible.
+
+Beside this file: tests/test_gan_ragged_gpu.py runs the D and G steps and generation off the
+golden shapes against the float64 restatement -- one engine across shrinking batches (160, 131,
+37, 5 and 2 rows; rows < batch_max on a workspace that still holds the larger batch), RMSprop,
+Adam and SGD in the fused optimizer epilogue at ks = 452, E = 12 and L = 260, histories with
+an all-padding row, a full row, a repeated item and an item in every row, real-slate hits at
+the tile, head and padding edges -- and tests/test_gan_autograd_cpu.py holds that restatement's
+backward to float64 autograd at such shapes.  tests/gan_common.py builds their inputs."""
 import os
 
 import numpy as np
@@ -18,6 +29,7 @@ import pytest
 import torch
 
 from oracle import gan as og
+from tests.gan_common import hist_and_slates, random_gan
 from tests.test_gan_oracle import key, load, param_ok
 
 pytestmark = pytest.mark.gpu
@@ -39,22 +51,41 @@ def gemm(A, B, a_km, b_km, M, N, K, post=0, splits=1, bias=None, ldc=None):
     return C[:, :N].cpu()
 
 
-@pytest.mark.parametrize("a_km,b_km", [(True, True), (True, False), (False, True), (False, False)])
-@pytest.mark.parametrize("M,N,K,splits", [(256, 512, 1000, 1), (250, 130, 64, 1), (64, 256, 2048, 7),
-                                          (300, 40, 36, 3),
-                                          (256, 512, 100544, 64)])   # C4's D layer 1 (S*N rounded to 4)
-def test_gemm_matches_float64(a_km, b_km, M, N, K, splits):
+LAYOUTS = [(True, True), (True, False), (False, True), (False, False)]
+GEMM_SHAPES = [(256, 512, 1000, 1), (250, 130, 64, 1), (64, 256, 2048, 7), (300, 40, 36, 3),
+               (256, 512, 100544, 64)]   # C4's D layer 1 (S*N rounded to 4)
+# K = rows of a ragged batch, as the weight-gradient GEMMs of both steps get it (M/N-major
+# operands only: K need not be a multiple of 4): K < one K step, K = 1, a ragged K step, and a
+# split whose last chunk is ragged (kc = 96: [0, 96) and [96, 131)); M = 130 and N = 130 give a
+# second tile of 2 rows / columns
+GEMM_RAGGED_K = [(130, 40, 37, 1), (64, 130, 131, 2), (33, 5, 1, 1), (40, 36, 5, 1)]
+K_TAIL = 32     # operand rows allocated past K, filled with NaN: only the K mask keeps them out
+
+
+def mn_major(x, K, tail):
+    """x (R, K) as an M/N-major operand [K + tail][round4(R)]: zero pad columns, NaN tail rows."""
+    R = x.shape[0]
+    out = torch.zeros(K + tail, (R + 3) // 4 * 4)
+    out[:K, :R] = x.t()
+    out[K:] = float("nan")
+    return out.contiguous().cuda()
+
+
+@pytest.mark.parametrize("M,N,K,splits,a_km,b_km",
+                         [c + l for c in GEMM_SHAPES for l in LAYOUTS] + [c + (False, False) for c in GEMM_RAGGED_K])
+def test_gemm_matches_float64(M, N, K, splits, a_km, b_km):
     if (a_km or b_km) and K % 4:
         pytest.skip("K-major operands need K % 4 == 0")
+    tail = K_TAIL if (M, N, K, splits) in GEMM_RAGGED_K else 0
     g = torch.Generator().manual_seed(M * 7 + N * 3 + K)
     a = torch.randn(M, K, generator=g)
     b = torch.randn(N, K, generator=g)
-    m4, n4 = (M + 3) // 4 * 4, (N + 3) // 4 * 4
-    A = (a if a_km else torch.cat([a.t(), torch.zeros(K, m4 - M)], 1)).contiguous().cuda()
-    B = (b if b_km else torch.cat([b.t(), torch.zeros(K, n4 - N)], 1)).contiguous().cuda()
+    A = a.contiguous().cuda() if a_km else mn_major(a, K, tail)
+    B = b.contiguous().cuda() if b_km else mn_major(b, K, tail)
     got = gemm(A, B, a_km, b_km, M, N, K, splits=splits)
     ref = a.double() @ b.double().t()
     bound = 2e-6 * (a.double().abs() @ b.double().abs().t()) + 1e-30
+    assert not got.isnan().any(), "operand rows past K reached the product"
     assert ((got.double() - ref).abs() <= bound).all()
 
 
@@ -66,7 +97,7 @@ def test_gemm_bias_tanh():
     assert (got.double() - ref).abs().max() < 2e-6
 
 
-@pytest.fixture(params=[0, 1], ids=["epilogue", "wave_specialised"])
+@pytest.fixture
 def gemm_ws(request):
     """Both forms of the optimizer GEMM (rg_gemm_ws_mode): the update in gemm_kernel's
     epilogue, and the wave-specialised persistent kernel."""
@@ -80,9 +111,21 @@ def gemm_ws(request):
     L.rg_gemm_ws_mode(prev)
 
 
-@pytest.mark.parametrize("M,N,K,ldp", [(512, 20000, 256, 20000),   # several tiles per workgroup (persistent)
-                                       (300, 1001, 64, 1004),      # K < 8 steps, ragged float4 tail column
-                                       (130, 5003, 640, 5003)])    # K > 8 steps, rows not float4-aligned
+RMS_SHAPES = [(512, 20000, 256, 20000),   # several tiles per workgroup (persistent)
+              (300, 1001, 64, 1004),      # K < 8 steps, ragged float4 tail column
+              (130, 5003, 640, 5003)]     # K > 8 steps, rows not float4-aligned
+# the D step's W1S gradient at N = 150, S = 3, H = 32 (ks = 452) on batches of 37 and 131 rows
+# (test_gan_ragged_gpu.py): K is no multiple of the K step, which only gemm_kernel's epilogue
+# form takes in either build, so these run in that form alone
+RMS_RAGGED_K = [(64, 450, 37, 452), (64, 450, 131, 452)]
+WS_FORMS = ["epilogue", "wave_specialised"]
+
+
+@pytest.mark.parametrize("gemm_ws,M,N,K,ldp",
+                         [(f,) + c for f in (0, 1) for c in RMS_SHAPES] + [(0,) + c for c in RMS_RAGGED_K],
+                         indirect=["gemm_ws"],
+                         ids=[f"{WS_FORMS[f]}-{'-'.join(map(str, c))}" for f in (0, 1) for c in RMS_SHAPES] +
+                             [f"epilogue-{'-'.join(map(str, c))}" for c in RMS_RAGGED_K])
 def test_gemm_rmsprop_matches_float64(M, N, K, ldp, gemm_ws):
     """The gradient GEMM fused with the RMSprop update (the cGAN's W1S / WH path,
     CGANs.py:440-457 RMSprop on D and G) against a float64 product + update of the
@@ -94,8 +137,8 @@ def test_gemm_rmsprop_matches_float64(M, N, K, ldp, gemm_ws):
     g = torch.Generator().manual_seed(M + N + K)
     a, b = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g)
     m4, n4 = (M + 3) // 4 * 4, (N + 3) // 4 * 4
-    A = torch.cat([a.t(), torch.zeros(K, m4 - M)], 1).contiguous().cuda()
-    B = torch.cat([b.t(), torch.zeros(K, n4 - N)], 1).contiguous().cuda()
+    tail = K_TAIL if (M, N, K, ldp) in RMS_RAGGED_K else 0
+    A, B = mn_major(a, K, tail), mn_major(b, K, tail)
     p0 = torch.randn(M, ldp, generator=g) * 0.01
     v0 = torch.rand(M, ldp, generator=g) * 1e-3
     P, V = p0.clone().cuda(), v0.clone().cuda()
@@ -109,6 +152,7 @@ def test_gemm_rmsprop_matches_float64(M, N, K, ldp, gemm_ws):
     pd = p0[:, :N].double() - lr * gd / (vd.sqrt() + eps)
     gb = 2e-6 * (a.double().abs() @ b.double().abs().t())
     Pg, Vg = P.cpu().double(), V.cpu().double()
+    assert not Pg.isnan().any() and not Vg.isnan().any(), "operand rows past K reached the update"
     assert ((Vg[:, :N] - vd).abs() <= 2 * gd.abs() * gb + 1e-6 * vd).all()
     # d(lr g / sqrt(v)) / dg <= lr * 2 / sqrt(v): the GEMM bound carried through, plus f32 rounding
     assert ((Pg[:, :N] - pd).abs() <= 2 * lr * gb / vd.sqrt() + 1e-6 * pd.abs() + 1e-9).all()
@@ -233,45 +277,6 @@ def test_gan_reference_init_clamp(golden_dir):
     for n in dn:
         before = np.clip(d_init[n], -og.CLAMP, og.CLAMP)
         assert np.abs(dsd[n].numpy() - before).max() <= 10 * lr * (1 + 1e-5), n
-
-
-def random_gan(N, S, H, E, Z, seed):
-    """Reference-shaped G / D state dicts (cGAN_models.py init: xavier weights, bias 0.01,
-    N(0,1) embeddings with a zero padding row, BatchNorm gamma 1 / beta 0)."""
-    g = torch.Generator().manual_seed(seed)
-    H1 = H // 2
-
-    def lin(o, i):
-        b = (6.0 / (i + o)) ** 0.5
-        return (torch.rand(o, i, generator=g) * 2 - 1) * b, torch.full((o,), 0.01)
-
-    def emb():
-        e = torch.randn(N + 1, E, generator=g)
-        e[N] = 0
-        return e
-
-    gs = {"embedding_layer.weight": emb()}
-    for pre, (o, i) in (("layers.0", (H1, Z + E)), ("layers.4", (H, H1))):
-        gs[pre + ".weight"], gs[pre + ".bias"] = lin(o, i)
-    for pre, w in (("layers.1", H1), ("layers.5", H)):
-        gs.update({pre + ".weight": torch.ones(w), pre + ".bias": torch.zeros(w), pre + ".running_mean": torch.zeros(w),
-                   pre + ".running_var": torch.ones(w), pre + ".num_batches_tracked": torch.tensor(0)})
-    for s in range(S):
-        gs[f"mult_heads.head_{s}.weight"], gs[f"mult_heads.head_{s}.bias"] = lin(N, H)
-    ds = {"embedding_layer.weight": emb()}
-    for pre, (o, i) in (("layers.0", (2 * H, S * N + E)), ("layers.3", (H, 2 * H)), ("layers.6", (H1, H)),
-                        ("layers.9", (1, H1))):
-        ds[pre + ".weight"], ds[pre + ".bias"] = lin(o, i)
-    return gs, ds
-
-
-def hist_and_slates(rs, rows, N, S, L):
-    hist = np.full((rows, L), N, np.int64)
-    for r in range(rows):
-        ln = rs.randint(0, L + 1)
-        hist[r, :ln] = rs.choice(N, ln, replace=False)
-    slates = np.stack([rs.choice(N, S, replace=False) for _ in range(rows)])
-    return hist, slates
 
 
 def test_gan_generate_fused_argmax():
