@@ -916,6 +916,8 @@ int rg_mf_score_users(void *stream, const float *user_w, const float *item_w,
  * precision_recall_score / hit_ratio / map_at_k read them (spotlight/evaluation.py:
  * 108-213, 278-353).  scores [rows][ld] (device, fp32), out_idx [rows][k] (device,
  * int32, rank order; equal scores: lower column first; NaN ranks last), 1 <= k <= 32.
+ * A row with fewer than k scores above -inf is filled with its -inf / NaN columns, lowest
+ * column first: every row gets k distinct columns in [0, cols).
  * ---------------------------------------------------------------------------- */
 int rg_topk_rows(void *stream, const float *scores, int64_t rows, int64_t cols, int64_t ld, int32_t k,
                  int32_t *out_idx);

@@ -40,17 +40,19 @@ __global__ __launch_bounds__(kTopkThreads) void topk_kernel(const float *__restr
         int xi = (int)c;
         if (x != x) x = -INFINITY;                       // NaN ranks last
         if (!topk_better(x, xi, v[K - 1], ix[K - 1])) continue;
-        // insert: carry the displaced element down the sorted list (static indices only)
+        // insert: carry the displaced element down the sorted list (static indices only).
+        // Selects, not a branch per slot: as a branch, the compiler's code for slot 0 lost
+        // an element that entered on the id alone (equal score, lower id), which is how a
+        // -inf entry meets the (-inf, INT_MAX) filler, and the filler's id came out instead.
 #pragma unroll
         for (int j = 0; j < K; ++j) {
-            if (topk_better(x, xi, v[j], ix[j])) {
-                const float tv = v[j];
-                const int ti = ix[j];
-                v[j] = x;
-                ix[j] = xi;
-                x = tv;
-                xi = ti;
-            }
+            const bool in = topk_better(x, xi, v[j], ix[j]);
+            const float tv = v[j];
+            const int ti = ix[j];
+            v[j] = in ? x : tv;
+            ix[j] = in ? xi : ti;
+            x = in ? tv : x;
+            xi = in ? ti : xi;
         }
     }
 #pragma unroll

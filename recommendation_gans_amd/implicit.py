@@ -413,6 +413,56 @@ class ImplicitFactorizationModel:
                                     int(k), _lib.ptr(out)), "rg_topk_rows")
         return out.cpu().numpy().astype(np.int64)
 
+    def recommend(self, user_ids, k=10, exclude=None, return_scores=False):
+        """The k best items for each of ``user_ids``: ``(len(user_ids), k)`` int64 item ids on the
+        host in rank order (higher score first, then the lower item id), with ``return_scores`` also
+        their float32 scores.  ``exclude``: an Interactions or a scipy sparse matrix of the model's
+        shape (typically the train set) whose items are left out per user; they have the score -inf
+        and are only returned, by id, to a user with fewer than k items left.
+
+        Works for every model the class trains (MF, NCF, NeuMF) and any number of users: the score
+        block of 4096 users at a time on the device (``_device_scores``), -inf over the excluded
+        entries, rg_topk_rows, and the scores gathered from the block at the returned ids; only ids
+        and scores come down.  After a data-parallel fit the gathered full tables are used, as in
+        ``predict``.  ValueError for an id outside the model, k < 1, k > min(32, num_items) or an
+        ``exclude`` of another shape."""
+        from . import _lib
+        users = np.asarray(user_ids, dtype=np.int64).reshape(-1)
+        k, n, num_items = int(k), len(users), self._num_items
+        if k < 1 or k > min(32, num_items):
+            raise ValueError("k must be in [1, min(32, num_items)]")
+        if n and (users.min() < 0 or users.max() >= self._num_users):
+            raise ValueError("user id outside [0, num_users)")
+        csr = None
+        if exclude is not None:
+            csr = exclude.tocsr()
+            if csr.shape != (self._num_users, num_items):
+                raise ValueError(f"exclude has shape {csr.shape}, the model {(self._num_users, num_items)}")
+        ids = np.empty((n, k), dtype=np.int64)
+        scores = np.empty((n, k), dtype=np.float32)
+        if n == 0:
+            return (ids, scores) if return_scores else ids
+        dev = self._engine.device
+        lib = _lib.load()
+        for s in range(0, n, 4096):
+            ub, blk = _score_block(self, users[s:s + 4096])
+            if csr is not None:
+                sub = csr[ub]
+                if sub.nnz:
+                    rows = np.repeat(np.arange(len(ub)), np.diff(sub.indptr))
+                    blk[torch.as_tensor(rows, device=dev),
+                        torch.as_tensor(sub.indices.astype(np.int64), device=dev)] = float("-inf")
+            out = torch.empty(len(ub), k, dtype=torch.int32, device=dev)
+            _lib.check(lib.rg_topk_rows(_lib.stream_handle(), _lib.ptr(blk), len(ub), num_items, num_items, k,
+                                        _lib.ptr(out)), "rg_topk_rows")
+            got = out.cpu().numpy()
+            if got.min() < 0 or got.max() >= num_items:         # never index the block with a bad id
+                raise RuntimeError("rg_topk_rows returned an item id outside the table")
+            ids[s:s + len(ub)] = got
+            if return_scores:
+                scores[s:s + len(ub)] = torch.gather(blk, 1, out.to(torch.int64)).cpu().numpy()
+        return (ids, scores) if return_scores else ids
+
     def rank_users(self, users, targets_csr, exclude_csr=None):
         """The rank of every item of ``targets_csr``'s rows in the full ranking of a block of
         users (evaluation.py:13-60, mrr_score: scipy rankdata of -score, ties averaged), counted
