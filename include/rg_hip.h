@@ -27,6 +27,7 @@
  *   rg_mf_score_users   BilinearNet.forward of a block of users against every item
  *                       (the block the ranking metrics read)
  *                                                          spotlight/evaluation.py:13-60, :115-213
+ *   rg_mf_topk_users    the k best items of those users, scored, excluded and ranked in LDS
  *   rg_loss_finalize    loss.item() of run_val_iteration    implicit.py:366-379
  *   rg_mf_stepper_*     the loop body of fit: one call per run_train_iteration
  *                                                          implicit.py:290-298, :347-364
@@ -910,6 +911,49 @@ int rg_mf_score_users(void *stream, const float *user_w, const float *item_w,
                       const float *user_b, const float *item_b, int32_t dim,
                       int64_t num_items, const int64_t *users_dev, int64_t n_users,
                       float *out_dev, int64_t ld);
+/* The k best items of each of those users without the score block (rg_mf_topk.hip), what
+ * recommend() reads.  Row r's key for column c is
+ *     -inf if c is in row r's exclusion list, else -inf if the score is NaN, else the score
+ * (the score of rg_mf_score_users: the same staging, product and epilogue code, the same
+ * bits), and
+ *     out_idx[r][0 .. k)    the k best columns by (key descending, column ascending): the
+ *                           order and fill rule of rg_topk_rows below -- k distinct columns
+ *                           in [0, num_items), never a filler id -- so the ids equal
+ *                           rg_mf_score_users, -inf over the exclusions, rg_topk_rows;
+ *     out_scores[r][j]      -inf for an excluded column, else the score itself (a NaN score
+ *                           as the NaN rg_mf_score_users writes); may be null.
+ * Both device, [n_users][k], int32 / fp32; 1 <= k <= min(32, num_items) <= INT_MAX.
+ * Exclusions are a CSR over the block's rows (device): row r's excluded columns are
+ * exc_idx[exc_ptr[r] .. exc_ptr[r + 1]), each row ASCENDING, repeats allowed; both null:
+ * none.  Every id is compared with the current tile's range before it is used: an id outside
+ * [0, num_items) is ignored, and a row that is not ascending may lose exclusions (a wrong
+ * ranking) but causes no access outside the tables.
+ * A workgroup (4 waves) per (group of RG_MF_SCORE_USER_GROUP users, split s of `splits`)
+ * walks the item tiles [s T / splits, (s + 1) T / splits) of the T = ceil(num_items /
+ * RG_MF_SCORE_ITEM_TILE) in ascending order: the scores of a tile go to LDS, not to memory,
+ * the exclusion cursors write -inf there, and four threads per user keep a sorted top-K
+ * (K = 8, 16 or 32) of their quarter of the row in registers; the four lists are merged in
+ * LDS after the last tile.  splits == 1 writes the outputs directly; otherwise k (score, id)
+ * pairs per (user, split) go to the workspace and a second small launch (a wave per user)
+ * selects the k best of them.  splits == 0: the library picks enough splits for three
+ * workgroups per compute unit of the current device (its attribute, asked for once and
+ * only after every refusal below), within [1, T].  (key, column) is a total
+ * order, so ids and scores do not depend on splits; no atomics.  workspace_dev holds
+ * rg_mf_topk_workspace_len bytes,
+ *     8 * n_users * k * splits        (splits == 0: the library's pick for these arguments),
+ * 4-byte aligned; with one split it is not touched.  The tables, users and exclusions are
+ * only read; users_dev ids are trusted to be in range, exc_ptr to describe exc_idx.
+ * Non-zero status (rg_last_error names the reason, no HIP call made) on a null table, users,
+ * workspace or out_idx pointer, only one of exc_ptr / exc_idx, dim outside [1, 256],
+ * num_items < 1 or above INT_MAX, n_users < 0, k outside [1, min(32, num_items)], splits < 0
+ * or above T, or more than 2^24 - 1 (user group, split) workgroups or 2^26 - 1 users (the
+ * length then is -1); n_users == 0: RG_OK, no launch. */
+int64_t rg_mf_topk_workspace_len(int64_t num_items, int64_t n_users, int32_t k, int32_t splits);
+int rg_mf_topk_users(void *stream, const float *user_w, const float *item_w,
+                     const float *user_b, const float *item_b, int32_t dim,
+                     int64_t num_items, const int64_t *users_dev, int64_t n_users,
+                     const int64_t *exc_ptr, const int32_t *exc_idx, int32_t k, int32_t splits,
+                     void *workspace_dev, int32_t *out_idx, float *out_scores);
 
 /* ------------------------------------------------------------------------------
  * Evaluation top-k (rg_eval.hip): the first k entries of argsort(-scores) per row, as

@@ -53,6 +53,17 @@ two broadcast adds, sigmoid) on the same tables and ids: 256 and 4096 users x ``
 d in {32, 64, 128}.  Device events, the two paths alternating; min / median per path, their ratio,
 the largest relative difference of the two blocks, and the kernel's time against max(flops at the
 fp32 MFMA peak, output bytes at the HBM peak).  One JSON line per shape.
+
+    python -m recommendation_gans_amd.eval_time --metric mf_topk [--items 26744] [--reps 20]
+
+times one block of MF ``recommend``: ``mf_engine.topk_users_fused`` (rg_mf_topk_users: score,
+exclude and rank in LDS) against the path it replaced, written out as one function -- the score
+block, -inf scattered from host-built indices, rg_topk_rows, the scores gathered at the ids.  Both
+start from host ids and a scipy CSR and end with ids and scores on the host, and must agree bit for
+bit.  256 and 4096 users x ``--items`` items at d in {32, 64, 128}, k = 10, with 100 excluded items
+per user and with none; the two paths alternating, device events and the host clock around the
+whole call, min / median per path, and the peak device memory of one call of each.  One JSON line
+per shape.
 """
 import argparse
 import contextlib
@@ -379,6 +390,101 @@ def main_mf_scores(args):
     return out
 
 
+def main_mf_topk(args):
+    """``--metric mf_topk``: one block of MF recommend, mf_engine.topk_users_fused against the path it
+    replaced (score block, -inf scatter from host-built indices, rg_topk_rows, gather)."""
+    import time
+
+    import scipy.sparse as sp
+
+    from . import _lib, mf_engine
+    from .implicit import _csr_rows_sorted
+    dev = torch.device("cuda:0")
+    U, I, k = 138493, args.items, 10
+    lib = _lib.load()
+    out = []
+
+    def replaced(tabs, ub, csr):
+        u = torch.as_tensor(ub, device=dev)
+        blk = mf_engine.score_users_block(*tabs, u)
+        if csr is not None:
+            sub = csr[ub]
+            if sub.nnz:
+                rows = np.repeat(np.arange(len(ub)), np.diff(sub.indptr))
+                blk[torch.as_tensor(rows, device=dev),
+                    torch.as_tensor(sub.indices.astype(np.int64), device=dev)] = float("-inf")
+        ids = torch.empty(len(ub), k, dtype=torch.int32, device=dev)
+        _lib.check(lib.rg_topk_rows(_lib.stream_handle(), _lib.ptr(blk), len(ub), I, I, k, _lib.ptr(ids)),
+                   "rg_topk_rows")
+        got = ids.cpu().numpy()
+        if got.min() < 0 or got.max() >= I:
+            raise RuntimeError("rg_topk_rows returned an item id outside the table")
+        return got, torch.gather(blk, 1, ids.to(torch.int64)).cpu().numpy()
+
+    def fused(tabs, ub, csr):
+        e_ptr, e_idx = _csr_rows_sorted(csr, ub) if csr is not None else (None, None)
+        ids, sc = mf_engine.topk_users_fused(*tabs, ub, k, e_ptr, e_idx, checked=True)
+        got = ids.cpu().numpy()
+        if got.min() < 0 or got.max() >= I:
+            raise RuntimeError("rg_mf_topk_users returned an item id outside the table")
+        return got, sc.cpu().numpy()
+
+    def clocked(fn):
+        """(device ms, host ms) of one call; the call ends with its results on the host."""
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b), (time.perf_counter() - t0) * 1e3
+
+    def peak(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        fn()
+        torch.cuda.synchronize()
+        return int(torch.cuda.max_memory_allocated() - base)
+
+    for d in (32, 64, 128):
+        g = torch.Generator().manual_seed(d)
+        tabs = [(torch.randn(U, d, generator=g) / d ** 0.5).to(dev), (torch.randn(I, d, generator=g) / d ** 0.5).to(dev),
+                (0.1 * torch.randn(U, generator=g)).to(dev), (0.1 * torch.randn(I, generator=g)).to(dev)]
+        for n in (256, 4096):
+            rs = np.random.RandomState(n)
+            ub = rs.choice(U, n, replace=False).astype(np.int64)
+            cols = np.concatenate([rs.choice(I, 100, replace=False) for _ in range(n)])
+            exc = sp.csr_matrix((np.ones(100 * n, np.float32), (np.repeat(ub, 100), cols)), shape=(U, I))
+            exc.sort_indices()
+            for csr, excluded in ((exc, 100), (None, 0)):
+                new = lambda: fused(tabs, ub, csr)
+                old = lambda: replaced(tabs, ub, csr)
+                for _ in range(3):                           # warm-up: code objects, allocator
+                    a, b = new(), old()
+                equal = bool((a[0] == b[0]).all() and a[1].tobytes() == b[1].tobytes())
+                del a, b
+                t_new, t_old = [], []
+                for _ in range(args.reps):                   # alternate the two paths
+                    t_new.append(clocked(new))
+                    t_old.append(clocked(old))
+                dn, hn = zip(*t_new)
+                do, ho = zip(*t_old)
+                r = {"metric": "mf_topk", "dim": d, "users": n, "items": I, "k": k, "excluded_per_user": excluded,
+                     "reps": args.reps, "equal": equal,
+                     "fused_device_ms": stats(dn), "fused_host_ms": stats(hn),
+                     "replaced_device_ms": stats(do), "replaced_host_ms": stats(ho),
+                     "host_median_ratio_replaced_over_fused": float(np.median(ho) / np.median(hn)),
+                     "device_median_ratio_replaced_over_fused": float(np.median(do) / np.median(dn)),
+                     "fused_peak_bytes": peak(new), "replaced_peak_bytes": peak(old), "block_bytes": 4 * n * I}
+                print(json.dumps(r), flush=True)
+                out.append(r)
+        del tabs
+        torch.cuda.empty_cache()
+    return out
+
+
 def main_scores(args):
     """The default mode: one block of ``--users`` users against every item, NCFEngine.score_users
     (rg_ncf_score_users) against the pairwise NCFEngine.scores_torch."""
@@ -426,7 +532,7 @@ def main_scores(args):
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--metric", choices=("scores", "mrr", "slates", "pairs", "mf_scores"), default="scores")
+    ap.add_argument("--metric", choices=("scores", "mrr", "slates", "pairs", "mf_scores", "mf_topk"), default="scores")
     ap.add_argument("--batch", type=int, default=8192)
     ap.add_argument("--users", type=int, default=None)
     ap.add_argument("--hist-len", type=int, default=128)
@@ -441,7 +547,7 @@ def main(argv=None):
     if args.reps is None:
         args.reps = 5 if slates or args.metric == "pairs" else 20
     return {"scores": main_scores, "mrr": main_mrr, "slates": main_slates, "pairs": main_pairs,
-            "mf_scores": main_mf_scores}[args.metric](args)
+            "mf_scores": main_mf_scores, "mf_topk": main_mf_topk}[args.metric](args)
 
 
 if __name__ == "__main__":

@@ -148,6 +148,55 @@ def score_users_block(U, I, ub, ib, users, checked=False):
     return out
 
 
+def topk_users_fused(U, I, ub, ib, users, k, exc_ptr=None, exc_idx=None, splits=0, checked=False):
+    """The k best items of ``users`` and their scores, ``(ids int32 [n, k], scores float32 [n, k])``
+    on the tables' device, in one fused launch (rg_mf_topk_users; a second small one merges the
+    item splits): the scores of ``score_users_block`` bit for bit, -inf over the excluded entries,
+    ranked by (score descending, item id ascending) as rg_topk_rows ranks them -- without the
+    (len(users), num_items) block.  ``exc_ptr`` (int64 [n + 1]) and ``exc_idx`` (int32) are a CSR
+    over the rows of ``users``, on the host or the device, each row's ids ASCENDING; an id outside
+    [0, num_items) is ignored; both None: nothing excluded.  ``splits``: item splits per user group
+    (0: the library picks).  The tables (those ``score_block_on_device`` accepts) are only read; a
+    user id outside [0, U.shape[0]) raises ValueError (one download of the ids' bounds;
+    ``checked=True``: the caller has checked these ids already)."""
+    if not score_block_on_device(U, I, ub, ib):
+        raise ValueError("topk_users_fused needs contiguous float32 tables of matching shapes on one CUDA device")
+    if (exc_ptr is None) != (exc_idx is None):
+        raise ValueError("exc_ptr and exc_idx go together")
+    dev = U.device
+    users = torch.as_tensor(users).to(dev, torch.int64).reshape(-1).contiguous()
+    n, num_items, k, splits = int(users.numel()), int(I.shape[0]), int(k), int(splits)
+    ids = torch.empty(n, k, dtype=torch.int32, device=dev)
+    scores = torch.empty(n, k, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    ws_len = int(lib.rg_mf_topk_workspace_len(num_items, n, k, splits))
+    if ws_len < 0:
+        raise ValueError("rg_mf_topk_workspace_len: " + lib.rg_last_error().decode(errors="replace"))
+    if n == 0:
+        return ids, scores
+    if not checked:
+        lo, hi = torch.stack(users.aminmax()).tolist()
+        if lo < 0 or hi >= U.shape[0]:
+            raise ValueError("user ids outside the user table")
+    if exc_ptr is not None:
+        exc_ptr = torch.as_tensor(exc_ptr).to(dev, torch.int64).reshape(-1).contiguous()
+        exc_idx = torch.as_tensor(exc_idx).to(dev, torch.int32).reshape(-1).contiguous()
+        if exc_ptr.numel() != n + 1:
+            raise ValueError("exc_ptr must have len(users) + 1 entries")
+        if not checked:                                 # the kernel trusts exc_ptr to describe exc_idx
+            bad = (exc_ptr[0] < 0) | (exc_ptr[-1] > exc_idx.numel()) | (exc_ptr[1:] < exc_ptr[:-1]).any()
+            if bool(bad):
+                raise ValueError("exc_ptr must ascend from >= 0 to <= len(exc_idx)")
+        if exc_idx.numel() == 0:                        # nothing to exclude (and no pointer to pass)
+            exc_ptr = exc_idx = None
+    ws = torch.empty(max(ws_len, 8) // 4, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.rg_mf_topk_users(_lib.stream_handle(), ptr(U), ptr(I), ptr(ub), ptr(ib), int(U.shape[1]), num_items,
+                                   ptr(users), n, ptr(exc_ptr), ptr(exc_idx), k, splits, ptr(ws), ptr(ids),
+                                   ptr(scores)), "rg_mf_topk_users")
+    return ids, scores
+
+
 MFPlan = namedtuple("MFPlan", "perm pos_slot item_slot_off n_planned", defaults=(None,))
 
 
