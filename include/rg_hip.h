@@ -1068,6 +1068,7 @@ enum rg_gan_d_block {
 enum rg_gan_ws_view {
     RG_GAN_WS_FAKE = 0,   /* G(z) of the last step: [rows][ks] */
     RG_GAN_WS_DOUT,       /* D outputs of the last step: D step [real rows | fake rows], G step [fake rows] */
+    RG_GAN_WS_A2,         /* G's last hidden activations (the heads' input) of the last forward: [rows][H] */
     RG_GAN_WS_END
 };
 
@@ -1120,6 +1121,49 @@ int rg_gan_g_step(void *stream, const rg_gan_model_t *model, void *workspace, co
 /* Eval-mode generator (BatchNorm running stats, no dropout): argmax slates [rows][S]. */
 int rg_gan_generate(void *stream, const rg_gan_model_t *model, void *workspace, const rg_gan_batch_t *batch,
                     const float *z, float *slates);
+
+/* Slates to serve from the eval-mode generator (the forward pass of rg_gan_generate: BatchNorm
+ * running statistics, no dropout, tanh heads), without repeats or already-seen items.  No
+ * counterpart in the reference, which only takes each head's argmax.  For row r with history
+ * hist[r][0..L) and the heads s = 0, 1, .., S - 1 in this order:
+ *     allowed(r, s) = { n in [0, N) : (not EXCLUDE_HISTORY or n not in hist[r]) and
+ *                                     (not DISTINCT        or n not in slates[r][0..s)) }
+ *     slates[r][s]  = the n in allowed(r, s) with the largest tanh(a2[r] . WH[s][n] + BH[s][n]);
+ *                     equal values (tanh saturates to exactly +-1.0f): the lower n;
+ *                     allowed(r, s) empty: N, the padding id.
+ * A NaN head output ranks below every number.  History ids outside [0, N) (the padding id
+ * included) are ignored and never used as an index.  flags == 0 gives rg_gan_generate's first
+ * maximum per head, as int32.  The batch carries only rows, hist_len and hist; workspace is the
+ * engine's (rg_gan_workspace_bytes); scratch (device, 16-byte aligned, sized for batch_max
+ * rows, every word read is written by the same call) holds
+ *     a history bitmap, ceil(N / 32) words per row (one launch, one workgroup per row; skipped
+ *     without EXCLUDE_HISTORY), and, where the fused path applies,
+ *     T (value, id) candidates per (row, 128-column tile of the S*N head columns, head segment),
+ *     T = 4 for S <= 4, else 8;
+ * rg_gan_recommend_scratch_bytes = 4 * batch_max * ceil(N / 32), rounded up to 16,
+ *     + 8 * batch_max * ceil(S * N / 128) * 2 * T where the fused path applies and path != 1;
+ * -1 (rg_last_error) on bad dims, S > 32, a path outside [0, 2] or path 2 where it cannot apply.
+ * path (a test and measurement selector, like splits of rg_mf_topk_users):
+ *     1  stored: the heads' tanh outputs go to the workspace's RG_GAN_WS_FAKE block as in
+ *        training, then one workgroup per row walks the heads in order over them (any N,
+ *        S <= 32; no atomics);
+ *     2  fused (N >= 128 and S <= 8): the head GEMM's epilogue keeps the T best allowed items
+ *        per (row, tile, segment) in registers and no rows x S*N block is written; one wave
+ *        per row then walks the heads in order over the candidates.  T >= S candidates are
+ *        enough: only the items taken by the at most S - 1 earlier heads can stand ahead of a
+ *        head's best allowed item in its tile's list;
+ *     0  the library's pick: fused where it applies, else stored.
+ * Both paths are deterministic and give the same ids whenever the two GEMM epilogues produce
+ * the same tanh bits (they run the same accumulation order).  Non-zero status (rg_last_error),
+ * decided before any HIP call: a null model / workspace / batch / z / scratch / slates, what
+ * the other rg_gan_* entries refuse (dims, rows outside [1, batch_max], an empty history),
+ * flags outside [0, 3], path outside [0, 2], path 2 with N < 128 or S > 8, S > 32, a scratch
+ * that is not 16-byte aligned. */
+#define RG_GAN_REC_EXCLUDE_HISTORY 1
+#define RG_GAN_REC_DISTINCT        2
+int64_t rg_gan_recommend_scratch_bytes(const rg_gan_dims_t *dims, int32_t path);
+int rg_gan_recommend(void *stream, const rg_gan_model_t *model, void *workspace, const rg_gan_batch_t *batch,
+                     const float *z, int32_t flags, int32_t path, void *scratch, int32_t *slates /* [rows][S] */);
 
 /* fp32 MFMA GEMM used by the cGAN (test entry): C = A B^T with A [M][K] (a_kmajor) or
  * [K][M], B [N][K] (b_kmajor) or [K][N]; post 0 none / 1 tanh; splits > 1 uses work

@@ -284,6 +284,23 @@ class CGAN:
             json.dump(res, fp)
         return res
 
+    def recommend(self, train_vec, exclude_history=True, distinct=True):
+        """A slate to serve for every row of ``train_vec`` (padded histories, as ``test`` takes
+        them): int64 (users, slate_size) on the host.  No counterpart in the reference, whose only
+        inference is each head's argmax: here the heads are taken in order, each the best item
+        that is not in the user's history (``exclude_history``) and not already in the slate
+        (``distinct``); equal head outputs go to the lower id, and ``num_items`` marks a slot for
+        which no item was left.  The histories go up once (``_history_chunks``, range-checked),
+        the selection runs on the device (GANEngine.recommend_slates) and the slates come down in
+        one copy.  ``test`` keeps the reference's argmax slates."""
+        if self.engine is None:
+            raise RuntimeError("call fit() first")
+        out = torch.empty(len(train_vec), self.slate_size, dtype=torch.int32, device=self.device)
+        for r0, hist in self._history_chunks(train_vec):
+            out[r0:r0 + hist.shape[0]] = self.engine.recommend_slates(hist, exclude_history=exclude_history,
+                                                                      distinct=distinct)
+        return out.cpu().to(torch.int64)
+
     def save_readable_model(self, model_save_dir, state_dict):
         fname = os.path.join(model_save_dir, "generator")
         logging.info("Saving state in {}".format(fname))

@@ -155,7 +155,10 @@ class GANNoise(ctypes.Structure):
 GAN_G_BLOCKS = ["WH", "BH", "EMB", "W1", "B1", "GAMMA1", "BETA1", "W2", "B2", "GAMMA2", "BETA2",
                 "RM1", "RV1", "RM2", "RV2"]
 GAN_D_BLOCKS = ["W1S", "EMB", "W1E", "B1", "W2", "B2", "W3", "B3", "W4", "B4"]
-GAN_WS_FAKE, GAN_WS_DOUT = 0, 1
+GAN_WS_FAKE, GAN_WS_DOUT, GAN_WS_A2 = 0, 1, 2
+# rg_gan_recommend flags and paths
+GAN_REC_EXCLUDE_HISTORY, GAN_REC_DISTINCT = 1, 2
+GAN_REC_PICK, GAN_REC_STORED, GAN_REC_FUSED = 0, 1, 2
 
 
 class MFLazy(ctypes.Structure):
@@ -194,6 +197,10 @@ SIGNATURES = [
                                      ctypes.c_void_p, ctypes.c_void_p]),
     ("rg_gan_generate", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(GANModel), ctypes.c_void_p,
                                        ctypes.POINTER(GANBatch), ctypes.c_void_p, ctypes.c_void_p]),
+    ("rg_gan_recommend_scratch_bytes", ctypes.c_int64, [ctypes.POINTER(GANDims), ctypes.c_int32]),
+    ("rg_gan_recommend", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(GANModel), ctypes.c_void_p,
+                                        ctypes.POINTER(GANBatch), ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                        ctypes.c_void_p, ctypes.c_void_p]),
     ("rg_gemm_ws_mode", ctypes.c_int, [ctypes.c_int32]),
     ("rg_gemm_f32_rms", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
                                        ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,

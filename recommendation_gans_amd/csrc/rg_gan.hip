@@ -20,6 +20,8 @@
 //                          the real rows as sparse column hits)
 #include "rg_gemm.h"
 
+#include <climits>
+
 namespace rg {
 namespace {
 
@@ -703,6 +705,144 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float *__restric
     slates[t] = (float)bi;
 }
 
+// ------------------------------------------------------------------ recommend (rg_gan_recommend)
+__device__ __forceinline__ bool pick_better(float v, int i, float bv, int bi) {
+    return v > bv || (v == bv && i < bi);
+}
+
+// (value descending, id ascending) best over the wave, in every lane
+__device__ __forceinline__ void wave_best(float &bv, int &bi) {
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ov = __shfl_xor(bv, off);
+        const int oi = __shfl_xor(bi, off);
+        if (pick_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+}
+
+// history bitmap: bits[row][w] bit b = item 32 w + b occurs in hist[row][0..L).  One workgroup
+// per row builds kBitChunk words at a time in LDS (LDS atomics: an OR per history entry, the
+// result independent of their order) and writes every word of the row; ids outside [0, N)
+// (the padding id) are skipped and never index anything
+constexpr int kBitChunk = 4096;
+__global__ __launch_bounds__(256) void hist_bits_kernel(const int32_t *__restrict__ hist, int L, int64_t N,
+                                                        int64_t words, uint32_t *__restrict__ bits) {
+    __shared__ uint32_t lds[kBitChunk];
+    const int t = threadIdx.x;
+    const int32_t *h = hist + (int64_t)blockIdx.x * L;
+    uint32_t *out = bits + (int64_t)blockIdx.x * words;
+    for (int64_t w0 = 0; w0 < words; w0 += kBitChunk) {
+        const int nw = (int)min((int64_t)kBitChunk, words - w0);
+        for (int w = t; w < nw; w += 256) lds[w] = 0u;
+        __syncthreads();
+        for (int l = t; l < L; l += 256) {
+            const int64_t id = h[l];
+            if (id < 0 || id >= N) continue;
+            const int64_t w = (id >> 5) - w0;
+            if (w >= 0 && w < nw) atomicOr(&lds[w], 1u << (id & 31));
+        }
+        __syncthreads();
+        for (int w = t; w < nw; w += 256) out[w0 + w] = lds[w];
+        __syncthreads();
+    }
+}
+
+// stored path: one workgroup per row walks the heads in order over the tanh outputs
+// T[row][s*N .. (s+1)*N).  Per head every thread scans its strided columns, skipping the
+// bitmap's items (bits null: none) and, with `distinct`, the ids of the heads before (LDS);
+// the best by (value descending, id ascending; NaN as -inf) is reduced over the wave by
+// shuffles and over the four waves through LDS, written, and the next head follows.
+// No allowed item left: the padding id N.  No atomics.
+constexpr int kPickMaxS = 32;
+__global__ __launch_bounds__(256) void slate_pick_kernel(const float *__restrict__ T, int64_t ld, int S, int64_t N,
+                                                         const uint32_t *__restrict__ bits, int64_t words,
+                                                         int distinct, int32_t *__restrict__ slates) {
+    __shared__ int chosen[kPickMaxS];
+    __shared__ float wv[4];
+    __shared__ int wi[4];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int64_t m = blockIdx.x;
+    const uint32_t *hb = bits ? bits + m * words : nullptr;
+    for (int s = 0; s < S; ++s) {
+        const float *row = T + m * ld + (int64_t)s * N;
+        float bv = -INFINITY;
+        int bi = INT_MAX;
+        for (int64_t n = t; n < N; n += 256) {
+            if (hb && ((hb[n >> 5] >> (n & 31)) & 1u)) continue;
+            bool taken = false;
+            if (distinct)
+                for (int q = 0; q < s; ++q) taken |= chosen[q] == (int)n;
+            if (taken) continue;
+            float v = row[n];
+            if (v != v) v = -INFINITY;
+            if (pick_better(v, (int)n, bv, bi)) { bv = v; bi = (int)n; }
+        }
+        wave_best(bv, bi);
+        if (lane == 0) { wv[wave] = bv; wi[wave] = bi; }
+        __syncthreads();
+        if (t == 0) {
+            for (int w = 1; w < 4; ++w)
+                if (pick_better(wv[w], wi[w], bv, bi)) { bv = wv[w]; bi = wi[w]; }
+            chosen[s] = bi;                       // INT_MAX (nothing left) matches no id
+            slates[m * S + s] = bi == INT_MAX ? (int32_t)N : bi;
+        }
+        __syncthreads();
+    }
+}
+
+// fused path: the slate from the top-T candidate lists of the head GEMM's epilogue (rg_gemm.hip
+// kEpiTopT, where the argument why T >= S entries per list are enough is written out).  One
+// wave per row walks the heads in order; for head s each lane takes, from each of its column
+// tiles overlapping the head, the first candidate not chosen by a head before (the lists are
+// sorted, so that is the tile's best allowed item), and the wave reduces by (value
+// descending, id ascending).  No candidate left: the padding id N.
+template <int TT>
+__global__ __launch_bounds__(256) void slate_final_kernel(const SlateCand *__restrict__ cand, int rows, int64_t ntile,
+                                                          int S, int64_t N, int distinct,
+                                                          int32_t *__restrict__ slates) {
+    const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (m >= rows) return;
+    int chosen[TT];
+#pragma unroll
+    for (int s = 0; s < TT; ++s) chosen[s] = -1;
+#pragma unroll
+    for (int s = 0; s < TT; ++s) {
+        if (s >= S) break;
+        const int64_t c0 = (int64_t)s * N, c1 = c0 + N;
+        const int64_t t0 = c0 / kGemmBN, t1 = std::min<int64_t>((c1 + kGemmBN - 1) / kGemmBN, ntile);
+        float bv = -INFINITY;
+        int bi = INT_MAX;
+        for (int64_t tile = t0 + lane; tile < t1; tile += 64) {
+            const int seg = (int)(s - tile * kGemmBN / N);
+            if (seg < 0 || seg > 1) continue;
+            const float4 *p = reinterpret_cast<const float4 *>(cand + ((m * ntile + tile) * 2 + seg) * TT);
+            float cv[TT];
+            int ci[TT];
+#pragma unroll
+            for (int j = 0; j < TT; j += 2) {
+                const float4 x = p[j / 2];
+                cv[j] = x.x; ci[j] = __float_as_int(x.y);
+                cv[j + 1] = x.z; ci[j + 1] = __float_as_int(x.w);
+            }
+            bool found = false;
+#pragma unroll
+            for (int j = 0; j < TT; ++j) {
+                bool taken = false;
+                if (distinct) {
+#pragma unroll
+                    for (int q = 0; q < s; ++q) taken |= ci[j] == chosen[q];
+                }
+                const bool use = !found && !taken;
+                found |= use;
+                if (use && pick_better(cv[j], ci[j], bv, bi)) { bv = cv[j]; bi = ci[j]; }
+            }
+        }
+        wave_best(bv, bi);
+        chosen[s] = bi;                           // INT_MAX (nothing left) matches no id but the filler's
+        if (lane == 0) slates[m * S + s] = bi == INT_MAX ? (int32_t)N : bi;
+    }
+}
+
 unsigned blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 void colsum(hipStream_t st, const float *X, int64_t rows, int64_t C, int64_t ld, const float *w, float *out) {
@@ -942,6 +1082,7 @@ extern "C" int64_t rg_gan_workspace_offset(const rg_gan_dims_t *dims, int32_t vi
     const Ws w = make_ws(m, go, dof);
     if (view == RG_GAN_WS_FAKE) return w.fake * 4;
     if (view == RG_GAN_WS_DOUT) return w.dval * 4;
+    if (view == RG_GAN_WS_A2) return w.a2 * 4;
     return -1;
 }
 
@@ -1174,4 +1315,103 @@ extern "C" int rg_gan_generate(void *stream, const rg_gan_model_t *mdl, void *wo
     hipLaunchKernelGGL(argmax_final_kernel, dim3((unsigned)(((int64_t)B * m.S + 3) / 4)), dim3(256), 0, x.st, d.amax, B,
                        gemm_tiles_n(m.SN), (int)m.S, m.N, slates);
     return check_launch("rg_gan_generate");
+}
+
+// ------------------------------------------------------------------ recommend
+namespace {
+
+constexpr int kRecMaxS = 32, kRecFusedMaxS = 8;
+
+bool rec_dims_ok(const rg_gan_dims_t &dm) {
+    return dm.num_items > 0 && dm.slate_size > 0 && dm.hidden >= 2 && dm.hidden % 8 == 0 && dm.emb_dim > 0 &&
+           dm.z_dim > 0 && dm.batch_max > 0;
+}
+
+bool rec_fused_applies(const rg_gan_dims_t &dm) {
+    return dm.num_items >= kGemmBN && dm.slate_size <= kRecFusedMaxS;
+}
+
+int rec_topt(int S) { return S <= 4 ? 4 : 8; }
+
+int64_t r16(int64_t x) { return (x + 15) / 16 * 16; }
+
+int64_t rec_words(int64_t N) { return (N + 31) / 32; }
+
+// scratch carve-up (bytes): bitmap [batch_max][words] | candidates [batch_max][tiles][2][T]
+int64_t rec_bitmap_bytes(const rg_gan_dims_t &dm) { return r16(4 * (int64_t)dm.batch_max * rec_words(dm.num_items)); }
+
+int64_t rec_cand_bytes(const rg_gan_dims_t &dm) {
+    return 8 * (int64_t)dm.batch_max * gemm_tiles_n((int64_t)dm.slate_size * dm.num_items) * 2 *
+           rec_topt(dm.slate_size);
+}
+
+}  // namespace
+
+extern "C" int64_t rg_gan_recommend_scratch_bytes(const rg_gan_dims_t *dims, int32_t path) {
+    const char *msg = nullptr;
+    if (!dims) msg = "null dims";
+    else if (!rec_dims_ok(*dims)) msg = "bad dims (hidden must be a positive multiple of 8)";
+    else if (dims->slate_size > kRecMaxS) msg = "slate_size above 32";
+    else if (path < 0 || path > 2) msg = "path must be 0 (the library's pick), 1 (stored) or 2 (fused)";
+    else if (path == 2 && !rec_fused_applies(*dims)) msg = "the fused path needs num_items >= 128 and slate_size <= 8";
+    if (msg) {
+        set_error(std::string("rg_gan_recommend_scratch_bytes: ") + msg);
+        return -1;
+    }
+    return rec_bitmap_bytes(*dims) + (path != 1 && rec_fused_applies(*dims) ? rec_cand_bytes(*dims) : 0);
+}
+
+extern "C" int rg_gan_recommend(void *stream, const rg_gan_model_t *mdl, void *workspace, const rg_gan_batch_t *bt,
+                                const float *z, int32_t flags, int32_t path, void *scratch, int32_t *slates) {
+    if (!mdl || !workspace || !bt || !z || !scratch || !slates)
+        return fail_arg("rg_gan_recommend: null model / workspace / batch / z / scratch / slates");
+    RG_TRY(check_common(mdl, workspace, bt));
+    const rg_gan_dims_t &dm = mdl->dims;
+    if (flags < 0 || flags > (RG_GAN_REC_EXCLUDE_HISTORY | RG_GAN_REC_DISTINCT))
+        return fail_arg("rg_gan_recommend: flags must be a combination of RG_GAN_REC_EXCLUDE_HISTORY and "
+                        "RG_GAN_REC_DISTINCT");
+    if (path < 0 || path > 2)
+        return fail_arg("rg_gan_recommend: path must be 0 (the library's pick), 1 (stored) or 2 (fused)");
+    if (dm.slate_size > kRecMaxS) return fail_arg("rg_gan_recommend: slate_size above 32");
+    if (path == 2 && !rec_fused_applies(dm))
+        return fail_arg("rg_gan_recommend: the fused path needs num_items >= 128 and slate_size <= 8");
+    if (reinterpret_cast<uintptr_t>(scratch) & 15) return fail_arg("rg_gan_recommend: scratch must be 16-byte aligned");
+    const bool fused = path == 2 || (path == 0 && rec_fused_applies(dm));
+    const Dims m(dm);
+    int64_t go[RG_GAN_G_END + 1], dof[RG_GAN_D_END + 1];
+    const Ws w = make_ws(m, go, dof);
+    const Ctx x{(hipStream_t)stream, m, go, dof, w, (char *)workspace};
+    const int B = bt->rows;
+    const int distinct = (flags & RG_GAN_REC_DISTINCT) ? 1 : 0;
+    const int64_t words = rec_words(m.N);
+    uint32_t *bits = nullptr;
+    if (flags & RG_GAN_REC_EXCLUDE_HISTORY) {
+        bits = reinterpret_cast<uint32_t *>(scratch);
+        hipLaunchKernelGGL(hist_bits_kernel, dim3((unsigned)B), dim3(256), 0, x.st, bt->hist, bt->hist_len, m.N, words,
+                           bits);
+    }
+    RG_TRY(g_forward(x, mdl, bt, z, nullptr, 0, false, false));
+    if (!fused) {
+        RG_TRY(g_heads(x, mdl, B));
+        hipLaunchKernelGGL(slate_pick_kernel, dim3((unsigned)B), dim3(256), 0, x.st, x.f(w.fake), m.ks, (int)m.S, m.N,
+                           bits, words, distinct, slates);
+        return check_launch("rg_gan_recommend");
+    }
+    GemmDesc d;
+    d.A = x.f(w.a2); d.lda = m.H;
+    d.B = mdl->g + go[RG_GAN_G_WH]; d.ldb = m.H;
+    d.M = B; d.N = m.SN; d.K = m.H;
+    d.epi = kEpiTopT; d.bias = mdl->g + go[RG_GAN_G_BH]; d.seg = m.N;
+    d.topt = rec_topt((int)m.S);
+    d.hbits = bits; d.hwords = words;
+    d.cand = reinterpret_cast<SlateCand *>(reinterpret_cast<char *>(scratch) + rec_bitmap_bytes(dm));
+    RG_TRY(gemm(x.st, d));
+    const dim3 grid((unsigned)((B + 3) / 4));
+    if (d.topt == 4)
+        hipLaunchKernelGGL((slate_final_kernel<4>), grid, dim3(256), 0, x.st, d.cand, B, gemm_tiles_n(m.SN), (int)m.S,
+                           m.N, distinct, slates);
+    else
+        hipLaunchKernelGGL((slate_final_kernel<8>), grid, dim3(256), 0, x.st, d.cand, B, gemm_tiles_n(m.SN), (int)m.S,
+                           m.N, distinct, slates);
+    return check_launch("rg_gan_recommend");
 }

@@ -19,6 +19,7 @@ enum GemmEpi {
     kEpiPartial = 1,  // C + z * M * N  <- acc (split-K partial, row stride N)
     kEpiOpt = 2,      // in-place optimizer update of P[m][n] with g = acc + hits
     kEpiArgmax = 3,   // per (row, column tile, head segment) argmax of tanh(acc + bias[n])
+    kEpiTopT = 4,     // per (row, column tile, head segment) the topt best of tanh(acc + bias[n])
 };
 
 enum GemmPost {
@@ -29,6 +30,13 @@ enum GemmPost {
 };
 
 constexpr int kGemmBM = 128, kGemmBN = 128, kGemmBK = 32;
+
+// a slate candidate of the top-T epilogue: head output and item id inside the head;
+// the filler (-inf, INT32_MAX) ranks after every item
+struct SlateCand {
+    float v;
+    int32_t id;
+};
 
 struct GemmDesc {
     const float *A = nullptr;
@@ -65,6 +73,13 @@ struct GemmDesc {
     // argmax: heads of `seg` columns; amax[(m * n_tiles + tile) * 2 + s] = (value, index)
     int64_t seg = 0;
     float2 *amax = nullptr;
+    // top-T (topt = 4 or 8): heads of `seg` columns; cand[((m * n_tiles + tile) * 2 + s) * topt + j],
+    // j = 0 .. topt - 1 in (value descending, id ascending) order, filler last.  Item i of row m
+    // is left out when bit i & 31 of hbits[m * hwords + (i >> 5)] is set (hbits null: none is)
+    int topt = 0;
+    const uint32_t *hbits = nullptr;
+    int64_t hwords = 0;
+    SlateCand *cand = nullptr;
 };
 
 int gemm(hipStream_t stream, const GemmDesc &d);

@@ -5,8 +5,8 @@
 // Operands are staged through LDS; the next step's global loads are in flight (in
 // registers) while the current step's 64 MFMAs per wave issue.  One LDS stage and two
 // barriers per K step (33.8 KB, <= 168 registers: 3 workgroups per CU) for every
-// epilogue but the argmax, which keeps two stages (one barrier per step) for its LDS
-// tile: at 2 workgroups per CU the lock-stepped workgroups of a CU left the matrix
+// epilogue but the argmax (and the top-T beside it), which keeps two stages (one barrier
+// per step) for its LDS tile: at 2 workgroups per CU the lock-stepped workgroups of a CU left the matrix
 // cores idle through each other's epilogues (cGAN 144k -> 166k slates/s).  K-major operands sit in LDS as [row][k] (stride 36 floats, 4 * odd
 // mod 64: the ds_read_b128 lane groups of a 32-row column read are conflict-free);
 // M/N-major operands as [k][row] (stride 132), read with ds_read_b32 across
@@ -20,6 +20,7 @@
 #include "rg_gemm.h"
 
 #include <atomic>
+#include <climits>
 
 namespace rg {
 
@@ -126,6 +127,27 @@ __device__ __forceinline__ bool better(float v, float i, float bv, float bi) {
     return v > bv || (v == bv && i < bi);
 }
 
+__device__ __forceinline__ bool cand_better(float v, int i, float bv, int bi) {
+    return v > bv || (v == bv && i < bi);
+}
+
+// insert (x, xi) into a list sorted by (value descending, id ascending), the displaced
+// element carried down with selects over static indices (rg_eval.hip topk_kernel: a branch
+// per slot lost an element that entered on the id alone)
+template <int T>
+__device__ __forceinline__ void cand_insert(float (&v)[T], int (&ix)[T], float x, int xi) {
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+        const bool in = cand_better(x, xi, v[j], ix[j]);
+        const float tv = v[j];
+        const int ti = ix[j];
+        v[j] = in ? x : tv;
+        ix[j] = in ? xi : ti;
+        x = in ? tv : x;
+        xi = in ? ti : xi;
+    }
+}
+
 __device__ __forceinline__ void opt1(const rg_opt_t &o, float clampv, float &p, float g, float &m, float &v) {
     float q = p;
     if (clampv > 0.0f) q = fminf(fmaxf(q, -clampv), clampv);
@@ -142,8 +164,9 @@ __device__ __forceinline__ void opt4(const rg_opt_t &o, float clampv, float4 &p,
 
 // ONE: a single operand stage (two barriers per K step) for 3 workgroups per CU instead
 // of 2 -- the LDS (33.8 KB) and register budget (<= 168 per lane) of three; the argmax
-// epilogue needs the double-buffered footprint for its tile
-template <bool AK, bool BKM, int EPI, bool ONE>
+// and top-T epilogues need the double-buffered footprint for their tile.  TT: the top-T
+// epilogue's list length
+template <bool AK, bool BKM, int EPI, bool ONE, int TT = 0>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(ONE ? 3 : 1, 8))) void gemm_kernel(GemmDesc d) {
     constexpr int kSA = Stage<AK>::kFloats, kSB = Stage<BKM>::kFloats;
     constexpr int kStages = ONE ? 1 : 2;
@@ -415,6 +438,82 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(ONE ? 
             const int64_t ntile = gemm_tiles_n(d.N);
             d.amax[(m * ntile + nt) * 2 + 0] = make_float2(bv[0], bi[0]);
             d.amax[(m * ntile + nt) * 2 + 1] = make_float2(bv[1], bi[1]);
+        }
+    } else if constexpr (EPI == kEpiTopT) {
+        // the argmax epilogue's tile and its two threads per row, each keeping the TT best
+        // (value descending, id ascending; NaN as -inf) of its 64 columns per head segment
+        // in registers.  An item whose bit is set in the row's bitmap never enters a list.
+        //
+        // Why TT >= S candidates per (row, tile, head) are enough for a slate of S heads
+        // taken in order, each head skipping the items of the heads before it: the best
+        // allowed item of head s sits in some tile; bitmap items are not in the lists; so
+        // in that tile's order only items taken by the s <= S - 1 earlier heads can stand
+        // ahead of it, and it is among the first S <= TT entries.
+        constexpr int LDT = BN + 1;
+        static_assert(2 * kSA + 2 * kSB >= BM * LDT && !ONE, "LDS reuse");
+        float *tile = smem;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int64_t n = col_of(j);
+                const float bn = (n < d.N && d.bias) ? d.bias[n] : 0.0f;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int rl = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    tile[rl * LDT + wn * 64 + j * 32 + l32] = tanhf(acc[i][j][r] + bn);
+                }
+            }
+        __syncthreads();
+        const int rl = tid >> 1, half = tid & 1;
+        const int64_t m = m0 + rl, h0 = n0 / d.seg;
+        const int id0 = (int)(n0 - h0 * d.seg);                        // item of tile column 0 (head h0)
+        const int cb = (int)min((int64_t)BN, (h0 + 1) * d.seg - n0);   // first tile column of head h0 + 1
+        const int cend = (int)min((int64_t)BN, d.N - n0);              // columns of the tile in use
+        const uint32_t *hb = (d.hbits && m < d.M) ? d.hbits + m * d.hwords : nullptr;
+        float tv[2][TT];
+        int ti[2][TT];
+#pragma unroll
+        for (int sg = 0; sg < 2; ++sg)
+#pragma unroll
+            for (int j = 0; j < TT; ++j) { tv[sg][j] = -INFINITY; ti[sg][j] = INT_MAX; }
+        uint32_t word = 0;
+        int wi = -1;
+        for (int c = half * 64; c < min(half * 64 + 64, cend); ++c) {
+            const bool second = c >= cb;
+            const int ix = second ? c - cb : id0 + c;
+            if (hb) {
+                if ((ix >> 5) != wi) { wi = ix >> 5; word = hb[wi]; }
+                if ((word >> (ix & 31)) & 1u) continue;
+            }
+            float v = tile[rl * LDT + c];
+            if (v != v) v = -INFINITY;
+            if (!second) {
+                if (cand_better(v, ix, tv[0][TT - 1], ti[0][TT - 1])) cand_insert<TT>(tv[0], ti[0], v, ix);
+            } else {
+                if (cand_better(v, ix, tv[1][TT - 1], ti[1][TT - 1])) cand_insert<TT>(tv[1], ti[1], v, ix);
+            }
+        }
+        // the other half's lists (disjoint columns) inserted into this one's
+#pragma unroll
+        for (int sg = 0; sg < 2; ++sg) {
+            float ov[TT];
+            int oi[TT];
+#pragma unroll
+            for (int j = 0; j < TT; ++j) { ov[j] = __shfl_xor(tv[sg][j], 1); oi[j] = __shfl_xor(ti[sg][j], 1); }
+#pragma unroll
+            for (int j = 0; j < TT; ++j) cand_insert<TT>(tv[sg], ti[sg], ov[j], oi[j]);
+        }
+        if (half == 0 && m < d.M) {
+            const int64_t ntile = gemm_tiles_n(d.N);
+            // two candidates per 16-byte store (the lists start on 32-byte boundaries)
+            float4 *out = reinterpret_cast<float4 *>(d.cand + (m * ntile + nt) * 2 * TT);
+#pragma unroll
+            for (int sg = 0; sg < 2; ++sg)
+#pragma unroll
+                for (int j = 0; j < TT; j += 2)
+                    out[(sg * TT + j) / 2] = make_float4(tv[sg][j], __int_as_float(ti[sg][j]), tv[sg][j + 1],
+                                                         __int_as_float(ti[sg][j + 1]));
         }
     }
 }
@@ -720,6 +819,10 @@ void launch_epi(hipStream_t stream, const GemmDesc &d, dim3 grid) {
         case kEpiStore: hipLaunchKernelGGL((gemm_kernel<AK, BKM, kEpiStore, true>), grid, dim3(kThreads), 0, stream, d); break;
         case kEpiPartial: hipLaunchKernelGGL((gemm_kernel<AK, BKM, kEpiPartial, true>), grid, dim3(kThreads), 0, stream, d); break;
         case kEpiOpt: hipLaunchKernelGGL((gemm_kernel<AK, BKM, kEpiOpt, true>), grid, dim3(kThreads), 0, stream, d); break;
+        case kEpiTopT:
+            if (d.topt == 4) hipLaunchKernelGGL((gemm_kernel<AK, BKM, kEpiTopT, false, 4>), grid, dim3(kThreads), 0, stream, d);
+            else hipLaunchKernelGGL((gemm_kernel<AK, BKM, kEpiTopT, false, 8>), grid, dim3(kThreads), 0, stream, d);
+            break;
         default: hipLaunchKernelGGL((gemm_kernel<AK, BKM, kEpiArgmax, false>), grid, dim3(kThreads), 0, stream, d); break;
     }
 }
@@ -757,6 +860,8 @@ int gemm(hipStream_t stream, const GemmDesc &d) {
     if (d.b_kmajor ? d.ldb < d.K : d.ldb < n4) return fail_arg("gemm: ldb too small");
     if (d.splits < 1 || (d.splits > 1 && d.epi != kEpiPartial)) return fail_arg("gemm: split-K needs kEpiPartial");
     if (d.epi == kEpiArgmax && (d.seg < kGemmBN || !d.amax)) return fail_arg("gemm: argmax needs seg >= 128");
+    if (d.epi == kEpiTopT && (d.seg < kGemmBN || !d.cand || (d.topt != 4 && d.topt != 8) || (d.hbits && d.hwords < 1)))
+        return fail_arg("gemm: top-T needs seg >= 128, cand and topt 4 or 8");
     if (d.epi == kEpiOpt && !d.P) return fail_arg("gemm: optimizer epilogue needs P");
     if (d.n_hits > 0 && (!d.hit_tile_off || !d.hit_col || !d.hit_row || !d.hit_src))
         return fail_arg("gemm: hits need hit_col, hit_row, hit_src and per-tile offsets");

@@ -64,6 +64,17 @@ bit.  256 and 4096 users x ``--items`` items at d in {32, 64, 128}, k = 10, with
 per user and with none; the two paths alternating, device events and the host clock around the
 whole call, min / median per path, and the peak device memory of one call of each.  One JSON line
 per shape.
+
+    python -m recommendation_gans_amd.eval_time --metric gan_recommend [--users 256] [--reps 20]
+
+times one batch of cGAN inference at the ``slates`` metric's shape (the ML-20M item count, S = 5,
+H = 256, E = 5, Z = 100, ``--users`` = batch_max rows, histories ``--hist-len`` wide) three ways on
+one engine and one z: rg_gan_generate (the per-head argmax, the baseline: not the code under
+measurement), and rg_gan_recommend with both flags on its stored path (tanh block written to the
+workspace, then one workgroup per row) and on its fused path (top-T candidates from the GEMM
+epilogue, no block).  Device events, the three alternating; min / median per path, the peak device
+memory torch saw during one call of each (the workspace and the scratch are allocated before), the
+sizes of the tanh block and of the scratch, and whether the two paths agree.  One JSON line.
 """
 import argparse
 import contextlib
@@ -485,6 +496,63 @@ def main_mf_topk(args):
     return out
 
 
+def main_gan_recommend(args):
+    """``--metric gan_recommend``: rg_gan_generate, and rg_gan_recommend's stored and fused paths, on
+    one batch at the slate evaluation's shape."""
+    import ctypes
+
+    from .gan_engine import GANBatch, GANEngine
+    from .spotlight.dnn_models.cGAN_models import discriminator, generator
+    from .synthetic import ML20M
+    dev = torch.device("cuda:0")
+    B, N, S, H, E, Z, L = args.users, ML20M["num_items"], 5, 256, 5, 100, args.hist_len
+    torch.manual_seed(0)
+    G = generator(num_items=N, noise_dim=Z, embedding_dim=E, hidden_layer=[H // 2, H], output_dim=S)
+    D = discriminator(num_items=N, embedding_dim=E, hidden_layers=[2 * H, H, H // 2], input_dim=S)
+    eng = GANEngine(G.state_dict(), D.state_dict(), N, S, H, E, Z, batch_max=B, device=dev)
+    del G, D
+    hist = slates_data(B, N, L)[0].numpy().astype(np.int64)
+    batch = GANBatch(hist, None, N, S, dev)
+    z = torch.rand(B, Z, device=dev)
+    paths = {"generate": lambda: eng.generate(batch, z=z),
+             "stored": lambda: eng.recommend_slates(batch.hist, z=z, path=1),
+             "fused": lambda: eng.recommend_slates(batch.hist, z=z, path=2)}
+    for _ in range(3):                                           # warm-up: code objects, the scratch, allocator
+        got = {k: fn() for k, fn in paths.items()}
+    torch.cuda.synchronize()
+    equal = bool(torch.equal(got["stored"], got["fused"]))
+    sl = got["fused"].cpu().numpy()
+    argmax = got["generate"].cpu().numpy().astype(np.int64)
+    ts = {k: [] for k in paths}
+    for _ in range(args.reps):                                   # alternate the three
+        for k, fn in paths.items():
+            ts[k] += timed(fn, 1)
+
+    def peak(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        fn()
+        torch.cuda.synchronize()
+        return int(torch.cuda.max_memory_allocated() - base)
+
+    r = {"metric": "gan_recommend", "rows": B, "items": N, "slate_size": S, "hidden": H, "emb": E, "z": Z,
+         "hist_len": L, "reps": args.reps,
+         "generate_ms": stats(ts["generate"]), "stored_ms": stats(ts["stored"]), "fused_ms": stats(ts["fused"]),
+         "fused_over_stored_median": float(np.median(ts["fused"]) / np.median(ts["stored"])),
+         "fused_over_generate_median": float(np.median(ts["fused"]) / np.median(ts["generate"])),
+         "peak_bytes": {k: peak(fn) for k, fn in paths.items()},
+         "tanh_block_bytes": 4 * B * S * N, "scratch_bytes": int(eng._rec_scratch.numel()),
+         "stored_scratch_bytes": int(eng.lib.rg_gan_recommend_scratch_bytes(ctypes.byref(eng.dims), 1)),
+         "workspace_bytes": int(eng.ws.numel()), "fused_equals_stored": equal,
+         "argmax_rows_with_a_repeat": int(sum(len(set(row)) < S for row in argmax.tolist())),
+         "argmax_rows_with_a_seen_item": int(sum(bool(set(a) & set(h)) for a, h in zip(argmax.tolist(), hist.tolist()))),
+         "recommend_rows_with_a_repeat_or_seen_item": int(sum(len(set(row)) < S or bool(set(row) & set(h))
+                                                              for row, h in zip(sl.tolist(), hist.tolist())))}
+    print(json.dumps(r), flush=True)
+    return [r]
+
+
 def main_scores(args):
     """The default mode: one block of ``--users`` users against every item, NCFEngine.score_users
     (rg_ncf_score_users) against the pairwise NCFEngine.scores_torch."""
@@ -532,7 +600,7 @@ def main_scores(args):
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--metric", choices=("scores", "mrr", "slates", "pairs", "mf_scores", "mf_topk"), default="scores")
+    ap.add_argument("--metric", choices=("scores", "mrr", "slates", "pairs", "mf_scores", "mf_topk", "gan_recommend"), default="scores")
     ap.add_argument("--batch", type=int, default=8192)
     ap.add_argument("--users", type=int, default=None)
     ap.add_argument("--hist-len", type=int, default=128)
@@ -547,7 +615,7 @@ def main(argv=None):
     if args.reps is None:
         args.reps = 5 if slates or args.metric == "pairs" else 20
     return {"scores": main_scores, "mrr": main_mrr, "slates": main_slates, "pairs": main_pairs,
-            "mf_scores": main_mf_scores, "mf_topk": main_mf_topk}[args.metric](args)
+            "mf_scores": main_mf_scores, "mf_topk": main_mf_topk, "gan_recommend": main_gan_recommend}[args.metric](args)
 
 
 if __name__ == "__main__":

@@ -157,6 +157,7 @@ class GANEngine:
         self.ws = torch.zeros(int(self.lib.rg_gan_workspace_bytes(ctypes.byref(self.dims))), dtype=torch.uint8,
                               device=dev)
         self.batch_max = batch_max
+        self._rec_scratch = None    # rg_gan_recommend's scratch, allocated at the first recommend_slates
         self.g_steps = 0            # optimizer steps taken (Adam bias corrections)
         self.d_steps = 0
         self.bn_tracked = [0, 0]    # num_batches_tracked of the two BatchNorms
@@ -355,6 +356,44 @@ class GANEngine:
                                            ctypes.c_void_p(sl.data_ptr() + r0 * self.S * 4)), "rg_gan_generate")
         return sl.to(torch.int32)
 
+    def recommend_slates(self, hist, exclude_history=True, distinct=True, z=None, path=0):
+        """Slates to serve (rg_gan_recommend) for every row of ``hist`` (device int32 (users, L),
+        ids in [0, N], N = padding, as for ``generate_slates``): the heads are taken in order,
+        each the best item of its tanh outputs (equal values: the lower id) that is not in the
+        row's history (``exclude_history``) and not already in the row's slate (``distinct``); a
+        slot with no item left holds N.  With both off these are ``generate_slates``' ids.  One
+        ``torch.rand(rows, Z)`` and one call per consecutive block of at most ``batch_max`` rows,
+        in order, or the rows of ``z`` (device float32 (users, Z)) when given.  ``path``: 0 the
+        library's pick, 1 the stored path, 2 the fused one (a test and measurement selector).
+        The scratch is allocated once per engine.  Returns a device int32 (users, S) tensor; no
+        host synchronisation."""
+        if hist.dtype != torch.int32 or hist.dim() != 2 or hist.device != self.device or not hist.is_contiguous():
+            raise ValueError("hist must be a contiguous int32 (users, L) tensor on the engine's device")
+        users, L = hist.shape
+        if z is not None:
+            if z.dtype != torch.float32 or z.shape != (users, self.Z) or z.device != self.device or \
+                    not z.is_contiguous():
+                raise ValueError("z must be a contiguous float32 (users, Z) tensor on the engine's device")
+        flags = (_lib.GAN_REC_EXCLUDE_HISTORY if exclude_history else 0) | (_lib.GAN_REC_DISTINCT if distinct else 0)
+        if self._rec_scratch is None:
+            n = int(self.lib.rg_gan_recommend_scratch_bytes(ctypes.byref(self.dims), 0))
+            if n < 0:
+                check(1, "rg_gan_recommend_scratch_bytes")
+            self._rec_scratch = torch.empty(max(n, 16), dtype=torch.uint8, device=self.device)
+        sl = torch.empty(users, self.S, dtype=torch.int32, device=self.device)
+        model, stream = self._model(), self._stream()
+        b = _lib.GANBatch()
+        b.hist_len = L
+        for r0 in range(0, users, self.batch_max):
+            rows = min(self.batch_max, users - r0)
+            zb = torch.rand(rows, self.Z, device=self.device) if z is None else z[r0:r0 + rows]
+            b.rows = rows
+            b.hist = ctypes.c_void_p(hist.data_ptr() + r0 * L * 4)
+            check(self.lib.rg_gan_recommend(stream, ctypes.byref(model), ptr(self.ws), ctypes.byref(b), ptr(zb),
+                                            flags, int(path), ptr(self._rec_scratch),
+                                            ctypes.c_void_p(sl.data_ptr() + r0 * self.S * 4)), "rg_gan_recommend")
+        return sl
+
     def slate_hits(self, hist, tgt_ptr, tgt_idx, k, out=None):
         """Generates a slate for every row of ``hist`` (``generate_slates``) and marks, with one
         rg_slate_hits launch over all rows, which of each slate's first k items are among the
@@ -373,6 +412,10 @@ class GANEngine:
     def last_fake(self, rows):
         """G(z) of the last step, (rows, S*N)."""
         return self.workspace_view(_lib.GAN_WS_FAKE, (rows, self.ks))[:, :self.S * self.N]
+
+    def last_a2(self, rows):
+        """The heads' input of the last generator forward, (rows, H)."""
+        return self.workspace_view(_lib.GAN_WS_A2, (rows, self.H))
 
     def last_d_out(self, rows):
         return self.workspace_view(_lib.GAN_WS_DOUT, (rows,))
