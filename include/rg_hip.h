@@ -28,6 +28,9 @@
  *                       (the block the ranking metrics read)
  *                                                          spotlight/evaluation.py:13-60, :115-213
  *   rg_mf_topk_users    the k best items of those users, scored, excluded and ranked in LDS
+ *   rg_item_sim_topk    the k rows of an embedding table most similar to each query row
+ *                       (cosine or inner product; no reference counterpart), rg_row_rnorms
+ *                       its reciprocal row norms
  *   rg_loss_finalize    loss.item() of run_val_iteration    implicit.py:366-379
  *   rg_mf_stepper_*     the loop body of fit: one call per run_train_iteration
  *                                                          implicit.py:290-298, :347-364
@@ -954,6 +957,54 @@ int rg_mf_topk_users(void *stream, const float *user_w, const float *item_w,
                      int64_t num_items, const int64_t *users_dev, int64_t n_users,
                      const int64_t *exc_ptr, const int32_t *exc_idx, int32_t k, int32_t splits,
                      void *workspace_dev, int32_t *out_idx, float *out_scores);
+
+/* ------------------------------------------------------------------------------
+ * Item-to-item similarity (rg_item_sim.hip): the k rows of an embedding table most similar
+ * to each query row -- "more like this" -- without the (queries, rows) block.
+ *
+ * rg_row_rnorms: out[r] = 1 / sqrt(sum_k table[r][k]^2) for r < rows (table [rows][dim] and
+ * out [rows], device, fp32), exactly 0.0f where the sum is 0.  A row's squares are added in
+ * one fixed order that depends on dim alone (16 lanes per row, each over its columns in
+ * ascending order, then a butterfly), so a row's value is the same bits in any call, at any
+ * row count, from an aligned table (16-byte loads when dim % 4 == 0) or not.  No atomics.
+ * Non-zero status on a null pointer, dim < 1, rows < 0 or rows > 16 (2^31 - 1); rows == 0:
+ * RG_OK, no launch.
+ *
+ * rg_item_sim_topk: for query row q = queries_dev[r] and candidate row c < num_rows
+ *     dot = <table[q], table[c]>     the product of rg_mf_score_users (the same staging and
+ *                                    MFMA code): ONE fp32 accumulator chain, k ascending
+ *     sim = (dot * rnorm[q]) * rnorm[c]   rnorm given (cosine; rnorm as rg_row_rnorms writes
+ *                                         it): two fp32 multiplies in that order
+ *         = dot                           rnorm null (inner product)
+ * and with RG_SIM_EXCLUDE_SELF in flags the value of column c == q is -inf.  The key of a
+ * NaN value is -inf;
+ *     out_idx[r][0 .. k)   the k best columns by (key descending, column ascending), the order
+ *                          of rg_mf_topk_users;
+ *     out_sims[r][j]       their values (a NaN as it is, -inf for the excluded column); may be
+ *                          null.
+ * Both device, [n_queries][k], int32 / fp32.  1 <= k <= min(32, num_rows), and <= num_rows - 1
+ * with RG_SIM_EXCLUDE_SELF: there are always k candidates beside the excluded one, so neither
+ * it nor a filler id is output unless fewer than k rows have a key above -inf (NaN values: the
+ * ties at -inf go by column).  The grid, the tiles of RG_MF_SCORE_ITEM_TILE rows, the groups of
+ * RG_MF_SCORE_USER_GROUP queries, splits, the workspace (rg_item_sim_workspace_len bytes =
+ * 8 * n_queries * k * splits, 4-byte aligned, untouched with one split) and the second launch
+ * are those of rg_mf_topk_users; ids and values do not depend on splits.  dim in [1, 256].
+ * Query ids are compared with [0, num_rows) on the device before anything is read by them: a
+ * group of RG_MF_SCORE_USER_GROUP consecutive queries that holds an id outside gets the id -1
+ * and the value NaN in every row of the group, and nothing is gathered for it.  The table,
+ * rnorm and the queries are only read.  Non-zero status (rg_last_error names the reason, no
+ * HIP call made) on a null table, queries, workspace or out_idx, flag bits other than
+ * RG_SIM_EXCLUDE_SELF, dim outside [1, 256], num_rows < 1 or above INT_MAX, n_queries < 0, k
+ * outside its range, splits < 0 or above the tile count, or the launch limits of
+ * rg_mf_topk_users (the length then is -1); n_queries == 0: RG_OK, no launch.
+ * ---------------------------------------------------------------------------- */
+#define RG_SIM_EXCLUDE_SELF 1
+int rg_row_rnorms(void *stream, const float *table, int64_t rows, int32_t dim, float *out);
+int64_t rg_item_sim_workspace_len(int64_t num_rows, int64_t n_queries, int32_t k, int32_t splits);
+int rg_item_sim_topk(void *stream, const float *table, const float *rnorm, int32_t dim,
+                     int64_t num_rows, const int64_t *queries_dev, int64_t n_queries,
+                     int32_t flags, int32_t k, int32_t splits, void *workspace_dev,
+                     int32_t *out_idx, float *out_sims);
 
 /* ------------------------------------------------------------------------------
  * Evaluation top-k (rg_eval.hip): the first k entries of argsort(-scores) per row, as

@@ -21,6 +21,7 @@ RG_NCF_SCORE_USER_GROUP = 64
 RG_NCF_SCORE_PAIR_TILE = 128     # rg_ncf_score_pairs: pairs per tile (32 per wave)
 RG_MF_SCORE_ITEM_TILE = 128      # rg_mf_score_users: items per tile, users per group
 RG_MF_SCORE_USER_GROUP = 64
+RG_SIM_EXCLUDE_SELF = 1          # rg_item_sim_topk flags: the query's own row is -inf
 RG_RANK_CHUNK = 16               # rg_rank_rows: targets counted per pass over a row
 RG_RANK_MAX_COLS = 1 << 20       # rg_rank_rows: the exclusion bitmap's columns (LDS)
 RG_SLATE_HITS_ROWS_PER_BLOCK = 4  # rg_slate_hits: rows (waves) per workgroup
@@ -392,6 +393,13 @@ SIGNATURES = [
                                         ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p,
                                         ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
                                         ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("rg_row_rnorms", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                     ctypes.c_void_p]),
+    ("rg_item_sim_workspace_len", ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
+    ("rg_item_sim_topk", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                        ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+                                        ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_void_p]),
     ("rg_mf_stepper_mt_mode", ctypes.c_int32, [ctypes.c_void_p]),
     ("rg_mf_stepper_create", ctypes.c_void_p, [ctypes.POINTER(MFStepperConfig)]),
     ("rg_mf_stepper_destroy", ctypes.c_int, [ctypes.c_void_p]),

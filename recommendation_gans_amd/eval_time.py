@@ -65,6 +65,17 @@ per user and with none; the two paths alternating, device events and the host cl
 whole call, min / median per path, and the peak device memory of one call of each.  One JSON line
 per shape.
 
+    python -m recommendation_gans_amd.eval_time --metric item_sim [--items 26744] [--reps 20]
+
+times one block of ``similar_items``: ``mf_engine.row_rnorms`` + ``mf_engine.similar_rows``
+(rg_row_rnorms, then rg_item_sim_topk: product, cosine and ranking in LDS) against the chain of
+torch ops a user would write for it on the same device and table -- ``F.normalize``, ``mm``, -inf at
+each query's own column, ``torch.topk``.  256 and 4096 query ids on an ``--items`` x d table at d in
+{32, 64, 128}, k = 10, the query's own row excluded; ids on the device before and results on the
+device after on both sides.  Device events, the two paths alternating; min / median per path, the
+peak device memory of one call of each, the share of rows whose id sets agree (the chain's order of
+tied items is torch.topk's) and the largest difference of the similarities.  One JSON line per shape.
+
     python -m recommendation_gans_amd.eval_time --metric gan_recommend [--users 256] [--reps 20]
 
 times one batch of cGAN inference at the ``slates`` metric's shape (the ML-20M item count, S = 5,
@@ -496,6 +507,64 @@ def main_mf_topk(args):
     return out
 
 
+def main_item_sim(args):
+    """``--metric item_sim``: one block of similar_items, mf_engine.row_rnorms + similar_rows against
+    the torch chain F.normalize, mm, -inf at the own column, torch.topk."""
+    import torch.nn.functional as F
+
+    from . import mf_engine
+    dev = torch.device("cuda:0")
+    I, k = args.items, 10
+    out = []
+
+    def peak(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        fn()
+        torch.cuda.synchronize()
+        return int(torch.cuda.max_memory_allocated() - base)
+
+    for d in (32, 64, 128):
+        g = torch.Generator().manual_seed(d)
+        table = (torch.randn(I, d, generator=g) / d ** 0.5).to(dev)
+        for n in (256, 4096):
+            q = torch.from_numpy(np.random.RandomState(n).randint(0, I, n)).to(dev)
+            rows = torch.arange(n, device=dev)
+
+            def new():
+                return mf_engine.similar_rows(table, q, k, rnorm=mf_engine.row_rnorms(table), checked=True)
+
+            def old():
+                unit = F.normalize(table, dim=1)
+                sims = unit[q] @ unit.T
+                sims[rows, q] = float("-inf")
+                top = torch.topk(sims, k, dim=1)
+                return top.indices, top.values
+
+            for _ in range(3):                               # warm-up: code objects, GEMM algorithms, allocator
+                a, b = new(), old()
+            torch.cuda.synchronize()
+            ia, ib = a[0].cpu().numpy().astype(np.int64), b[0].cpu().numpy()
+            same = float(np.mean([set(x) == set(y) for x, y in zip(ia.tolist(), ib.tolist())]))
+            diff = float((a[1] - b[1]).abs().max())
+            del a, b
+            t_new, t_old = [], []
+            for _ in range(args.reps):                       # alternate the two paths
+                t_new += timed(new, 1)
+                t_old += timed(old, 1)
+            r = {"metric": "item_sim", "dim": d, "queries": n, "items": I, "k": k, "reps": args.reps,
+                 "kernel_ms": stats(t_new), "torch_ms": stats(t_old),
+                 "median_ratio_torch_over_kernel": float(np.median(t_old) / np.median(t_new)),
+                 "kernel_peak_bytes": peak(new), "torch_peak_bytes": peak(old), "block_bytes": 4 * n * I,
+                 "rows_with_equal_id_sets": same, "max_abs_sim_diff": diff}
+            print(json.dumps(r), flush=True)
+            out.append(r)
+        del table
+        torch.cuda.empty_cache()
+    return out
+
+
 def main_gan_recommend(args):
     """``--metric gan_recommend``: rg_gan_generate, and rg_gan_recommend's stored and fused paths, on
     one batch at the slate evaluation's shape."""
@@ -600,7 +669,8 @@ def main_scores(args):
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--metric", choices=("scores", "mrr", "slates", "pairs", "mf_scores", "mf_topk", "gan_recommend"), default="scores")
+    ap.add_argument("--metric", choices=("scores", "mrr", "slates", "pairs", "mf_scores", "mf_topk", "item_sim",
+                                        "gan_recommend"), default="scores")
     ap.add_argument("--batch", type=int, default=8192)
     ap.add_argument("--users", type=int, default=None)
     ap.add_argument("--hist-len", type=int, default=128)
@@ -615,7 +685,8 @@ def main(argv=None):
     if args.reps is None:
         args.reps = 5 if slates or args.metric == "pairs" else 20
     return {"scores": main_scores, "mrr": main_mrr, "slates": main_slates, "pairs": main_pairs,
-            "mf_scores": main_mf_scores, "mf_topk": main_mf_topk, "gan_recommend": main_gan_recommend}[args.metric](args)
+            "mf_scores": main_mf_scores, "mf_topk": main_mf_topk, "item_sim": main_item_sim,
+            "gan_recommend": main_gan_recommend}[args.metric](args)
 
 
 if __name__ == "__main__":

@@ -505,6 +505,57 @@ class ImplicitFactorizationModel:
                 scores[s:s + len(ub)] = torch.gather(blk, 1, out.to(torch.int64)).cpu().numpy()
         return (ids, scores) if return_scores else ids
 
+    def _item_table(self, space):
+        """The item embedding table ``similar_items`` compares, on the device: MF's item factors
+        (the gathered full table after a data-parallel fit), the NCF tower's item embeddings, or for
+        NeuMF the GMF item table (``space="mf"``) or the tower's (``space="mlp"``)."""
+        if self._kind == "mf":
+            return self._tables()[1]
+        return self._engine.mf_w[1] if space == "mf" else self._engine.item_w
+
+    def similar_items(self, item_ids, k=10, metric="cosine", include_self=False, space=None, return_scores=False):
+        """The k items most similar to each of ``item_ids`` ("more like this"): ``(len(item_ids), k)``
+        int64 item ids on the host in rank order (higher similarity first, then the lower item id),
+        with ``return_scores`` also their float32 similarities.  ``metric``: "cosine" or "dot" (the
+        inner product) of the item embeddings -- MF's item factors, the NCF tower's item embeddings,
+        and for NeuMF the table ``space`` names ("mf": the GMF item table, the default; "mlp": the
+        tower's; for MF and NCF it must be None).  The item itself is left out unless
+        ``include_self``.  Any number of ids, 4096 at a time through the fused kernel
+        (``mf_engine.similar_rows``: product, similarity and ranking in LDS, no (ids, items) block);
+        the reciprocal norms are computed once per call.  Only ids and similarities come down.
+        ValueError for an id outside [0, num_items), k < 1, k > min(32, num_items - 1) (num_items with
+        ``include_self``), an unknown ``metric`` or an unknown ``space``."""
+        items = np.asarray(item_ids, dtype=np.int64).reshape(-1)
+        k, n, num_items = int(k), len(items), self._num_items
+        if metric not in mf_engine.SIM_METRICS:
+            raise ValueError(f"unknown metric {metric!r}: one of {mf_engine.SIM_METRICS}")
+        if k < 1 or k > min(32, num_items - (0 if include_self else 1)):
+            raise ValueError("k must be in [1, min(32, num_items - 1)] (num_items with include_self)")
+        if n and (items.min() < 0 or items.max() >= num_items):
+            raise ValueError("item id outside [0, num_items)")
+        neumf = self._kind != "mf" and self._engine.neumf
+        if neumf and space is None:
+            space = "mf"
+        if space not in (("mf", "mlp") if neumf else (None,)):
+            raise ValueError(f"unknown space {space!r}: NeuMF has 'mf' (the GMF item table, the default) and 'mlp' "
+                             "(the tower's); MF and NCF have one item table and take None")
+        ids = np.empty((n, k), dtype=np.int64)
+        sims = np.empty((n, k), dtype=np.float32)
+        if n == 0:
+            return (ids, sims) if return_scores else ids
+        table = self._item_table(space)
+        rnorm = mf_engine.row_rnorms(table) if metric == "cosine" else None
+        for s in range(0, n, 4096):
+            out, sc = mf_engine.similar_rows(table, items[s:s + 4096], k, metric=metric, exclude_self=not include_self,
+                                             rnorm=rnorm, checked=True)
+            got = out.cpu().numpy()
+            if got.min() < 0 or got.max() >= num_items:     # before the ids are used for anything
+                raise RuntimeError("rg_item_sim_topk returned an item id outside the table")
+            ids[s:s + len(got)] = got
+            if return_scores:
+                sims[s:s + len(got)] = sc.cpu().numpy()
+        return (ids, sims) if return_scores else ids
+
     def rank_users(self, users, targets_csr, exclude_csr=None):
         """The rank of every item of ``targets_csr``'s rows in the full ranking of a block of
         users (evaluation.py:13-60, mrr_score: scipy rankdata of -score, ties averaged), counted

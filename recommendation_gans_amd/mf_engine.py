@@ -197,6 +197,74 @@ def topk_users_fused(U, I, ub, ib, users, k, exc_ptr=None, exc_idx=None, splits=
     return ids, scores
 
 
+SIM_METRICS = ("cosine", "dot")
+
+
+def _sim_table(table, what):
+    if not (torch.is_tensor(table) and table.is_cuda and table.dtype == torch.float32 and table.dim() == 2 and
+            table.is_contiguous() and 1 <= table.shape[1] <= 256 and table.shape[0] >= 1):
+        raise ValueError(f"{what} needs a contiguous float32 (rows, dim <= 256) table on a CUDA device")
+
+
+def row_rnorms(table):
+    """1 / sqrt(sum of squares) of every row of ``table`` (contiguous float32 (rows, dim) on a CUDA
+    device), float32 (rows,) on its device, exactly 0 for a zero row (rg_row_rnorms).  A row's value
+    is the same bits whatever the row count."""
+    _sim_table(table, "row_rnorms")
+    out = torch.empty(table.shape[0], dtype=torch.float32, device=table.device)
+    with torch.cuda.device(table.device):
+        check(_lib.load().rg_row_rnorms(_lib.stream_handle(), ptr(table), int(table.shape[0]), int(table.shape[1]),
+                                        ptr(out)), "rg_row_rnorms")
+    return out
+
+
+def similar_rows(table, queries, k, metric="cosine", exclude_self=True, rnorm=None, splits=0, checked=False):
+    """The k rows of ``table`` most similar to each row id of ``queries``: ``(ids int32 [n, k], sims
+    float32 [n, k])`` on the table's device, in one fused launch (rg_item_sim_topk; a second small
+    one merges the row splits), without the (queries, rows) block.  ``metric``: "cosine" --
+    ``(dot * rnorm[q]) * rnorm[c]`` with the reciprocal norms of ``row_rnorms`` (computed here unless
+    ``rnorm`` brings them) -- or "dot", the inner product itself.  Ranked by (similarity descending,
+    row id ascending), NaN last; ``exclude_self`` leaves the query's own row out (k <= rows - 1
+    then).  ``splits``: row splits per query group (0: the library picks).  The table (contiguous
+    float32 (rows, dim <= 256) on a CUDA device: anything else raises, there is no fall-back) is only
+    read; a query id outside [0, rows) raises ValueError (one download of the ids' bounds;
+    ``checked=True``: the caller has checked these ids already)."""
+    _sim_table(table, "similar_rows")
+    if metric not in SIM_METRICS:
+        raise ValueError(f"unknown metric {metric!r}: one of {SIM_METRICS}")
+    dev, rows = table.device, int(table.shape[0])
+    queries = torch.as_tensor(queries).to(dev, torch.int64).reshape(-1).contiguous()
+    n, k, splits = int(queries.numel()), int(k), int(splits)
+    if k < 1 or k > min(32, rows - (1 if exclude_self else 0)):
+        raise ValueError("k must be in [1, min(32, rows)] (rows - 1 with exclude_self)")
+    lib = _lib.load()
+    ws_len = int(lib.rg_item_sim_workspace_len(rows, n, k, splits))
+    if ws_len < 0:
+        raise ValueError("rg_item_sim_workspace_len: " + lib.rg_last_error().decode(errors="replace"))
+    ids = torch.empty(n, k, dtype=torch.int32, device=dev)
+    sims = torch.empty(n, k, dtype=torch.float32, device=dev)
+    if n == 0:
+        return ids, sims
+    if not checked:
+        lo, hi = torch.stack(queries.aminmax()).tolist()
+        if lo < 0 or hi >= rows:
+            raise ValueError("query ids outside the table")
+    if metric == "cosine":
+        if rnorm is None:
+            rnorm = row_rnorms(table)
+        elif not (torch.is_tensor(rnorm) and rnorm.device == dev and rnorm.dtype == torch.float32 and
+                  rnorm.is_contiguous() and rnorm.numel() == rows):
+            raise ValueError("rnorm must be a contiguous float32 tensor of one value per row on the table's device")
+    else:
+        rnorm = None
+    ws = torch.empty(max(ws_len, 8) // 4, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.rg_item_sim_topk(_lib.stream_handle(), ptr(table), ptr(rnorm), int(table.shape[1]), rows,
+                                   ptr(queries), n, _lib.RG_SIM_EXCLUDE_SELF if exclude_self else 0, k, splits,
+                                   ptr(ws), ptr(ids), ptr(sims)), "rg_item_sim_topk")
+    return ids, sims
+
+
 MFPlan = namedtuple("MFPlan", "perm pos_slot item_slot_off n_planned", defaults=(None,))
 
 
