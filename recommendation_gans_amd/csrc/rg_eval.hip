@@ -3,8 +3,8 @@
 // entries of each user's ranking, argsort(-scores)).
 //
 // One workgroup per user row: every thread keeps a sorted top-K of its strided slice
-// of the row in registers (insertion, K <= kTopkMax), the 256 lists are merged in LDS
-// by a tree of pairwise merges, and the row's k best item ids are written in rank
+// of the row in registers (rg_topk_lists.h's TopList, K <= kTopkMax), the 256 lists are
+// merged in LDS by its merge_tree, and the row's k best item ids are written in rank
 // order.  Order: higher score first, then the lower item id (numpy's default argsort
 // leaves the order of equal scores unspecified; for distinct scores the ranking is
 // the reference's).  Only users x k ids leave the device instead of the users x items
@@ -13,16 +13,13 @@
 #include <climits>
 
 #include "rg_common.h"
+#include "rg_topk_lists.h"
 
 namespace rg {
 namespace {
 
+using topk::kTopkMax;
 constexpr int kTopkThreads = 256;
-constexpr int kTopkMax = 32;
-
-__device__ __forceinline__ bool topk_better(float a, int ia, float b, int ib) {
-    return a > b || (a == b && ia < ib);
-}
 
 template <int K>
 __global__ __launch_bounds__(kTopkThreads) void topk_kernel(const float *__restrict__ scores, int64_t cols, int64_t ld,
@@ -31,52 +28,13 @@ __global__ __launch_bounds__(kTopkThreads) void topk_kernel(const float *__restr
     __shared__ int si[kTopkThreads * K];
     const int tid = threadIdx.x;
     const float *row = scores + (int64_t)blockIdx.x * ld;
-    float v[K];
-    int ix[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) { v[j] = -INFINITY; ix[j] = INT_MAX; }
-    for (int64_t c = tid; c < cols; c += kTopkThreads) {
-        float x = row[c];
-        int xi = (int)c;
-        if (x != x) x = -INFINITY;                       // NaN ranks last
-        if (!topk_better(x, xi, v[K - 1], ix[K - 1])) continue;
-        // insert: carry the displaced element down the sorted list (static indices only).
-        // Selects, not a branch per slot: as a branch, the compiler's code for slot 0 lost
-        // an element that entered on the id alone (equal score, lower id), which is how a
-        // -inf entry meets the (-inf, INT_MAX) filler, and the filler's id came out instead.
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            const bool in = topk_better(x, xi, v[j], ix[j]);
-            const float tv = v[j];
-            const int ti = ix[j];
-            v[j] = in ? x : tv;
-            ix[j] = in ? xi : ti;
-            x = in ? tv : x;
-            xi = in ? ti : xi;
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < K; ++j) { sv[tid * K + j] = v[j]; si[tid * K + j] = ix[j]; }
+    // only ids leave, so the lists carry a NaN's key (-inf) in the NaN's place: nothing in them is a NaN
+    topk::TopList<K, false> top;
+    top.init();
+    for (int64_t c = tid; c < cols; c += kTopkThreads) top.insert(topk::key_of(row[c]), (int)c);
+    top.store(sv + tid * K, si + tid * K);
     __syncthreads();
-    // tree merge: at stride s, thread t (t % 2s == 0) merges lists t and t + s into t
-    for (int s = 1; s < kTopkThreads; s <<= 1) {
-        if ((tid & (2 * s - 1)) == 0) {
-            const float *av = sv + tid * K, *bv = sv + (tid + s) * K;
-            const int *ai = si + tid * K, *bi = si + (tid + s) * K;
-            float mv[K];
-            int mi[K];
-            int p = 0, q = 0;
-            for (int j = 0; j < k; ++j) {
-                const bool take_a = topk_better(av[p], ai[p], bv[q], bi[q]);
-                mv[j] = take_a ? av[p] : bv[q];
-                mi[j] = take_a ? ai[p] : bi[q];
-                p += take_a ? 1 : 0;
-                q += take_a ? 0 : 1;
-            }
-            for (int j = 0; j < k; ++j) { sv[tid * K + j] = mv[j]; si[tid * K + j] = mi[j]; }
-        }
-        __syncthreads();
-    }
+    topk::merge_tree<K, kTopkThreads, false>(sv, si, tid);
     if (tid < k) out[(int64_t)blockIdx.x * k + tid] = si[tid];
 }
 

@@ -132,8 +132,8 @@ __device__ __forceinline__ bool cand_better(float v, int i, float bv, int bi) {
 }
 
 // insert (x, xi) into a list sorted by (value descending, id ascending), the displaced
-// element carried down with selects over static indices (rg_eval.hip topk_kernel: a branch
-// per slot lost an element that entered on the id alone)
+// element carried down with selects over static indices (rg_topk_lists.h TopList::insert: a
+// branch per slot lost an element that entered on the id alone)
 template <int T>
 __device__ __forceinline__ void cand_insert(float (&v)[T], int (&ix)[T], float x, int xi) {
 #pragma unroll

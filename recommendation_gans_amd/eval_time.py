@@ -419,28 +419,17 @@ def main_mf_topk(args):
 
     import scipy.sparse as sp
 
-    from . import _lib, mf_engine
-    from .implicit import _csr_rows_sorted
+    from . import mf_engine
+    from .implicit import _csr_rows_sorted, _exclude_csr_rows, _topk_block
     dev = torch.device("cuda:0")
     U, I, k = 138493, args.items, 10
-    lib = _lib.load()
     out = []
 
     def replaced(tabs, ub, csr):
         u = torch.as_tensor(ub, device=dev)
         blk = mf_engine.score_users_block(*tabs, u)
-        if csr is not None:
-            sub = csr[ub]
-            if sub.nnz:
-                rows = np.repeat(np.arange(len(ub)), np.diff(sub.indptr))
-                blk[torch.as_tensor(rows, device=dev),
-                    torch.as_tensor(sub.indices.astype(np.int64), device=dev)] = float("-inf")
-        ids = torch.empty(len(ub), k, dtype=torch.int32, device=dev)
-        _lib.check(lib.rg_topk_rows(_lib.stream_handle(), _lib.ptr(blk), len(ub), I, I, k, _lib.ptr(ids)),
-                   "rg_topk_rows")
-        got = ids.cpu().numpy()
-        if got.min() < 0 or got.max() >= I:
-            raise RuntimeError("rg_topk_rows returned an item id outside the table")
+        _exclude_csr_rows(blk, csr, ub)
+        ids, got = _topk_block(blk, k)
         return got, torch.gather(blk, 1, ids.to(torch.int64)).cpu().numpy()
 
     def fused(tabs, ub, csr):

@@ -81,6 +81,33 @@ def _score_block(model, users):
     return ub, model._device_scores(u).to(torch.float32).contiguous()
 
 
+def _exclude_csr_rows(blk, csr, rows):
+    """-inf into the score block ``blk`` (len(rows), num_items) at the entries of ``csr``'s ``rows``
+    (in that order); ``csr`` None: nothing."""
+    if csr is None:
+        return
+    sub = csr[rows]
+    if sub.nnz:
+        r = np.repeat(np.arange(len(rows)), np.diff(sub.indptr))
+        blk[torch.as_tensor(r, device=blk.device),
+            torch.as_tensor(sub.indices.astype(np.int64), device=blk.device)] = float("-inf")
+
+
+def _topk_block(blk, k):
+    """rg_topk_rows on a contiguous fp32 score block: its rows' k best column ids as (int32
+    [rows, k] on the device, the same on the host), range-checked before anything is indexed
+    with them."""
+    from . import _lib
+    n, cols = blk.shape
+    out = torch.empty(n, k, dtype=torch.int32, device=blk.device)
+    _lib.check(_lib.load().rg_topk_rows(_lib.stream_handle(), _lib.ptr(blk), n, cols, cols, int(k), _lib.ptr(out)),
+               "rg_topk_rows")
+    got = out.cpu().numpy()
+    if got.size and (got.min() < 0 or got.max() >= cols):
+        raise RuntimeError("rg_topk_rows returned an item id outside the table")
+    return out, got
+
+
 def _score_block_fits(n, num_items, device):
     """Whether recommend may build the (n, num_items) fp32 score block: twice its size within the
     device's free memory (the driver's free bytes plus what torch's allocator holds unused).  The
@@ -420,20 +447,9 @@ class ImplicitFactorizationModel:
         precision/recall@k, hit ratio, MAP@k), ranked on the device by rg_topk_rows;
         items of ``exclude_csr``'s rows rank last (the reference's FLOAT_MAX).  Returns
         (len(users), k) int64 on the host."""
-        from . import _lib
-        dev = self._engine.device
         ub, s = _score_block(self, users)
-        if exclude_csr is not None:
-            sub = exclude_csr[ub]
-            if sub.nnz:
-                rows = np.repeat(np.arange(len(ub)), np.diff(sub.indptr))
-                s[torch.as_tensor(rows, device=dev), torch.as_tensor(sub.indices.astype(np.int64), device=dev)] = \
-                    float("-inf")
-        out = torch.empty(len(ub), k, dtype=torch.int32, device=dev)
-        lib = _lib.load()
-        _lib.check(lib.rg_topk_rows(_lib.stream_handle(), _lib.ptr(s), len(ub), self._num_items, self._num_items,
-                                    int(k), _lib.ptr(out)), "rg_topk_rows")
-        return out.cpu().numpy().astype(np.int64)
+        _exclude_csr_rows(s, exclude_csr, ub)
+        return _topk_block(s, k)[1].astype(np.int64)
 
     def recommend(self, user_ids, k=10, exclude=None, return_scores=False):
         """The k best items for each of ``user_ids``: ``(len(user_ids), k)`` int64 item ids on the
@@ -453,7 +469,6 @@ class ImplicitFactorizationModel:
         ids and scores come down.  After a data-parallel fit the gathered full tables are used, as
         in ``predict``.  ValueError for an id outside the model, k < 1, k > min(32, num_items) or an
         ``exclude`` of another shape."""
-        from . import _lib
         users = np.asarray(user_ids, dtype=np.int64).reshape(-1)
         k, n, num_items = int(k), len(users), self._num_items
         if k < 1 or k > min(32, num_items):
@@ -470,7 +485,6 @@ class ImplicitFactorizationModel:
         if n == 0:
             return (ids, scores) if return_scores else ids
         dev = self._engine.device
-        lib = _lib.load()
         tables = self._tables() if self._kind == "mf" else None
         # asked once per call, for the largest block: the kernel where that block does not fit
         fused = tables is not None and mf_engine.score_block_on_device(*tables) and \
@@ -488,18 +502,8 @@ class ImplicitFactorizationModel:
                     scores[s:s + len(ub)] = sc.cpu().numpy()
                 continue
             ub, blk = _score_block(self, users[s:s + 4096])
-            if csr is not None:
-                sub = csr[ub]
-                if sub.nnz:
-                    rows = np.repeat(np.arange(len(ub)), np.diff(sub.indptr))
-                    blk[torch.as_tensor(rows, device=dev),
-                        torch.as_tensor(sub.indices.astype(np.int64), device=dev)] = float("-inf")
-            out = torch.empty(len(ub), k, dtype=torch.int32, device=dev)
-            _lib.check(lib.rg_topk_rows(_lib.stream_handle(), _lib.ptr(blk), len(ub), num_items, num_items, k,
-                                        _lib.ptr(out)), "rg_topk_rows")
-            got = out.cpu().numpy()
-            if got.min() < 0 or got.max() >= num_items:         # never index the block with a bad id
-                raise RuntimeError("rg_topk_rows returned an item id outside the table")
+            _exclude_csr_rows(blk, csr, ub)
+            out, got = _topk_block(blk, k)                      # checked: never index the block with a bad id
             ids[s:s + len(ub)] = got
             if return_scores:
                 scores[s:s + len(ub)] = torch.gather(blk, 1, out.to(torch.int64)).cpu().numpy()

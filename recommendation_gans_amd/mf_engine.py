@@ -148,6 +148,30 @@ def score_users_block(U, I, ub, ib, users, checked=False):
     return out
 
 
+def _topk_setup(ids, dev, k, splits, ws_len_fn, num_rows, limit, outside):
+    """What the fused top-k calls do ahead of their launch: ``ids`` on ``dev`` as contiguous int64,
+    the (n, k) int32 id and float32 value outputs, and the workspace of the library's
+    ``ws_len_fn(num_rows, n, k, splits)`` bytes (ValueError with the library's reason for a shape
+    it refuses).  ``limit`` not None: ValueError(``outside``) for an id outside [0, limit).
+    Returns (ids, out_ids, out_values, workspace); n == 0: nothing was checked beyond the shape
+    and there is no workspace (None)."""
+    ids = torch.as_tensor(ids).to(dev, torch.int64).reshape(-1).contiguous()
+    n = int(ids.numel())
+    out_ids = torch.empty(n, k, dtype=torch.int32, device=dev)
+    out_values = torch.empty(n, k, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    ws_len = int(getattr(lib, ws_len_fn)(num_rows, n, k, splits))
+    if ws_len < 0:
+        raise ValueError(ws_len_fn + ": " + lib.rg_last_error().decode(errors="replace"))
+    if n == 0:
+        return ids, out_ids, out_values, None
+    if limit is not None:
+        lo, hi = torch.stack(ids.aminmax()).tolist()
+        if lo < 0 or hi >= limit:
+            raise ValueError(outside)
+    return ids, out_ids, out_values, torch.empty(max(ws_len, 8) // 4, dtype=torch.int32, device=dev)
+
+
 def topk_users_fused(U, I, ub, ib, users, k, exc_ptr=None, exc_idx=None, splits=0, checked=False):
     """The k best items of ``users`` and their scores, ``(ids int32 [n, k], scores float32 [n, k])``
     on the tables' device, in one fused launch (rg_mf_topk_users; a second small one merges the
@@ -163,21 +187,12 @@ def topk_users_fused(U, I, ub, ib, users, k, exc_ptr=None, exc_idx=None, splits=
         raise ValueError("topk_users_fused needs contiguous float32 tables of matching shapes on one CUDA device")
     if (exc_ptr is None) != (exc_idx is None):
         raise ValueError("exc_ptr and exc_idx go together")
-    dev = U.device
-    users = torch.as_tensor(users).to(dev, torch.int64).reshape(-1).contiguous()
-    n, num_items, k, splits = int(users.numel()), int(I.shape[0]), int(k), int(splits)
-    ids = torch.empty(n, k, dtype=torch.int32, device=dev)
-    scores = torch.empty(n, k, dtype=torch.float32, device=dev)
-    lib = _lib.load()
-    ws_len = int(lib.rg_mf_topk_workspace_len(num_items, n, k, splits))
-    if ws_len < 0:
-        raise ValueError("rg_mf_topk_workspace_len: " + lib.rg_last_error().decode(errors="replace"))
+    dev, num_items, k, splits = U.device, int(I.shape[0]), int(k), int(splits)
+    users, ids, scores, ws = _topk_setup(users, dev, k, splits, "rg_mf_topk_workspace_len", num_items,
+                                         None if checked else U.shape[0], "user ids outside the user table")
+    n = int(users.numel())
     if n == 0:
         return ids, scores
-    if not checked:
-        lo, hi = torch.stack(users.aminmax()).tolist()
-        if lo < 0 or hi >= U.shape[0]:
-            raise ValueError("user ids outside the user table")
     if exc_ptr is not None:
         exc_ptr = torch.as_tensor(exc_ptr).to(dev, torch.int64).reshape(-1).contiguous()
         exc_idx = torch.as_tensor(exc_idx).to(dev, torch.int32).reshape(-1).contiguous()
@@ -189,9 +204,8 @@ def topk_users_fused(U, I, ub, ib, users, k, exc_ptr=None, exc_idx=None, splits=
                 raise ValueError("exc_ptr must ascend from >= 0 to <= len(exc_idx)")
         if exc_idx.numel() == 0:                        # nothing to exclude (and no pointer to pass)
             exc_ptr = exc_idx = None
-    ws = torch.empty(max(ws_len, 8) // 4, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        check(lib.rg_mf_topk_users(_lib.stream_handle(), ptr(U), ptr(I), ptr(ub), ptr(ib), int(U.shape[1]), num_items,
+        check(_lib.load().rg_mf_topk_users(_lib.stream_handle(), ptr(U), ptr(I), ptr(ub), ptr(ib), int(U.shape[1]), num_items,
                                    ptr(users), n, ptr(exc_ptr), ptr(exc_idx), k, splits, ptr(ws), ptr(ids),
                                    ptr(scores)), "rg_mf_topk_users")
     return ids, scores
@@ -232,23 +246,14 @@ def similar_rows(table, queries, k, metric="cosine", exclude_self=True, rnorm=No
     _sim_table(table, "similar_rows")
     if metric not in SIM_METRICS:
         raise ValueError(f"unknown metric {metric!r}: one of {SIM_METRICS}")
-    dev, rows = table.device, int(table.shape[0])
-    queries = torch.as_tensor(queries).to(dev, torch.int64).reshape(-1).contiguous()
-    n, k, splits = int(queries.numel()), int(k), int(splits)
+    dev, rows, k, splits = table.device, int(table.shape[0]), int(k), int(splits)
     if k < 1 or k > min(32, rows - (1 if exclude_self else 0)):
         raise ValueError("k must be in [1, min(32, rows)] (rows - 1 with exclude_self)")
-    lib = _lib.load()
-    ws_len = int(lib.rg_item_sim_workspace_len(rows, n, k, splits))
-    if ws_len < 0:
-        raise ValueError("rg_item_sim_workspace_len: " + lib.rg_last_error().decode(errors="replace"))
-    ids = torch.empty(n, k, dtype=torch.int32, device=dev)
-    sims = torch.empty(n, k, dtype=torch.float32, device=dev)
+    queries, ids, sims, ws = _topk_setup(queries, dev, k, splits, "rg_item_sim_workspace_len", rows,
+                                         None if checked else rows, "query ids outside the table")
+    n = int(queries.numel())
     if n == 0:
         return ids, sims
-    if not checked:
-        lo, hi = torch.stack(queries.aminmax()).tolist()
-        if lo < 0 or hi >= rows:
-            raise ValueError("query ids outside the table")
     if metric == "cosine":
         if rnorm is None:
             rnorm = row_rnorms(table)
@@ -257,9 +262,8 @@ def similar_rows(table, queries, k, metric="cosine", exclude_self=True, rnorm=No
             raise ValueError("rnorm must be a contiguous float32 tensor of one value per row on the table's device")
     else:
         rnorm = None
-    ws = torch.empty(max(ws_len, 8) // 4, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        check(lib.rg_item_sim_topk(_lib.stream_handle(), ptr(table), ptr(rnorm), int(table.shape[1]), rows,
+        check(_lib.load().rg_item_sim_topk(_lib.stream_handle(), ptr(table), ptr(rnorm), int(table.shape[1]), rows,
                                    ptr(queries), n, _lib.RG_SIM_EXCLUDE_SELF if exclude_self else 0, k, splits,
                                    ptr(ws), ptr(ids), ptr(sims)), "rg_item_sim_topk")
     return ids, sims
