@@ -28,6 +28,8 @@
  *                       (the block the ranking metrics read)
  *                                                          spotlight/evaluation.py:13-60, :115-213
  *   rg_mf_topk_users    the k best items of those users, scored, excluded and ranked in LDS
+ *   rg_topk_rows_wide   the first k <= 1024 entries of argsort(-scores) of a score block
+ *                                                          spotlight/evaluation.py:115-213
  *   rg_item_sim_topk    the k rows of an embedding table most similar to each query row
  *                       (cosine or inner product; no reference counterpart), rg_row_rnorms
  *                       its reciprocal row norms
@@ -1016,6 +1018,30 @@ int rg_item_sim_topk(void *stream, const float *table, const float *rnorm, int32
  * ---------------------------------------------------------------------------- */
 int rg_topk_rows(void *stream, const float *scores, int64_t rows, int64_t cols, int64_t ld, int32_t k,
                  int32_t *out_idx);
+
+/* ------------------------------------------------------------------------------
+ * Top-k beyond 32 (rg_topk_wide.hip): the same ranking for 1 <= k <= RG_TOPK_WIDE_MAX, what the
+ * metrics read at the cut-offs 50 and 100.  scores [rows][ld] (device, fp32, only read; columns
+ * [cols, ld) are padding and never read), out_idx [rows][k] (device, int32): the first k columns
+ * of each row in the order of rg_topk_rows -- key descending, then column ascending, the key of
+ * a NaN is -inf, -0.0 and +0.0 are one key -- so for k <= 32 the ids are rg_topk_rows' ids,
+ * its fill rule included: a row with fewer than k scores above -inf is completed with its
+ * -inf / NaN columns, lowest column first, and every row gets k distinct columns in [0, cols).
+ * out_val [rows][k] (device, fp32; may be null): the row's raw value at each returned column (a
+ * NaN stays the NaN it was).
+ * One workgroup per row: each value maps to an order-preserving 32-bit key, four 8-bit radix
+ * passes with LDS histograms find the k-th key, a fifth pass collects the columns above it and,
+ * by an ordered compaction (no atomic places a tied column), the lowest-numbered columns equal to
+ * it; the k survivors are sorted in LDS.  The row is read five times, after the first from cache.
+ * Deterministic (integer counts and compares).  No workspace, no device allocation.
+ * rg_topk_rows stays the kernel for k <= 32 (one pass over the row).
+ * Non-zero status (rg_last_error), before any HIP call, on a null scores / out_idx, rows < 0,
+ * cols < 1, ld < cols, cols or rows above INT_MAX, or k outside [1, min(RG_TOPK_WIDE_MAX,
+ * cols)]; rows == 0: RG_OK, no launch.
+ * ---------------------------------------------------------------------------- */
+#define RG_TOPK_WIDE_MAX 1024
+int rg_topk_rows_wide(void *stream, const float *scores, int64_t rows, int64_t cols, int64_t ld,
+                      int32_t k, int32_t *out_idx, float *out_val);
 
 /* ------------------------------------------------------------------------------
  * Evaluation ranks (rg_eval.hip): where given items stand in each row's full ranking,

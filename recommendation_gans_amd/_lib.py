@@ -22,6 +22,7 @@ RG_NCF_SCORE_PAIR_TILE = 128     # rg_ncf_score_pairs: pairs per tile (32 per wa
 RG_MF_SCORE_ITEM_TILE = 128      # rg_mf_score_users: items per tile, users per group
 RG_MF_SCORE_USER_GROUP = 64
 RG_SIM_EXCLUDE_SELF = 1          # rg_item_sim_topk flags: the query's own row is -inf
+RG_TOPK_WIDE_MAX = 1024          # rg_topk_rows_wide: the largest k (rg_topk_rows: 32)
 RG_RANK_CHUNK = 16               # rg_rank_rows: targets counted per pass over a row
 RG_RANK_MAX_COLS = 1 << 20       # rg_rank_rows: the exclusion bitmap's columns (LDS)
 RG_SLATE_HITS_ROWS_PER_BLOCK = 4  # rg_slate_hits: rows (waves) per workgroup
@@ -262,6 +263,8 @@ SIGNATURES = [
     ("rg_mf_stepper_tail_gen", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(MTGen)]),
     ("rg_topk_rows", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                      ctypes.c_int32, ctypes.c_void_p]),
+    ("rg_topk_rows_wide", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                          ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
     ("rg_rank_rows", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                      ctypes.c_void_p, ctypes.c_void_p]),

@@ -86,6 +86,18 @@ workspace, then one workgroup per row) and on its fused path (top-T candidates f
 epilogue, no block).  Device events, the three alternating; min / median per path, the peak device
 memory torch saw during one call of each (the workspace and the scratch are allocated before), the
 sizes of the tanh block and of the scratch, and whether the two paths agree.  One JSON line.
+
+    python -m recommendation_gans_amd.eval_time --metric topk_wide [--items 26744] [--reps 20]
+
+times rg_topk_rows_wide (radix select, k up to 1024) on one score block of 256 and of 4096 users x
+``--items`` items that is already on the device, at k = 50, 100 and 1024: device events, the ids
+left on the device.  Beside it, alternating on the same block: (a) the host path it replaces in
+the @k metrics above k = 32 -- the block copied to the host, negated, one ``argsort`` per row in a
+Python loop, the first k -- on the host clock, 2 repetitions at 256 users and 1 at 4096 (the line
+says how many); (b) ``torch.topk(blk, k)``, for information only: its order of tied scores is
+unspecified, so it is no replacement, and the line gives the share of rows whose id sets agree.
+Each block size also gets a k = 32 line, the new entry against rg_topk_rows (reported only: the old
+kernel keeps k <= 32).  One JSON line per block size and k.
 """
 import argparse
 import contextlib
@@ -554,6 +566,92 @@ def main_item_sim(args):
     return out
 
 
+def main_topk_wide(args):
+    """``--metric topk_wide``: rg_topk_rows_wide on one score block already on the device, against
+    the host path it replaces in the @k metrics above k = 32 (the block to the host, argsort per row)
+    and, for information, torch.topk; and at k = 32 against rg_topk_rows."""
+    import time
+
+    from . import _lib
+    dev = torch.device("cuda:0")
+    I = args.items
+    lib = _lib.load()
+    out = []
+
+    def wide(blk, ids, k):
+        _lib.check(lib.rg_topk_rows_wide(_lib.stream_handle(), _lib.ptr(blk), blk.shape[0], I, I, k, _lib.ptr(ids),
+                                         None), "rg_topk_rows_wide")
+
+    def narrow(blk, ids, k):
+        _lib.check(lib.rg_topk_rows(_lib.stream_handle(), _lib.ptr(blk), blk.shape[0], I, I, k, _lib.ptr(ids)),
+                   "rg_topk_rows")
+
+    def host(blk, k):
+        """What evaluation._scored / _ranked do with a block: download, negate, argsort per row."""
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        scores = -blk.cpu().numpy()
+        top = np.empty((len(scores), k), dtype=np.int64)
+        for r in range(len(scores)):
+            top[r] = scores[r].argsort(axis=0)[:k]
+        return (time.perf_counter() - t0) * 1e3, top
+
+    for n in (256, 4096):
+        # sigmoid of a normal logit, as a trained model's block: one magnitude, many shared leading bits
+        blk = torch.sigmoid(torch.randn(n, I, generator=torch.Generator().manual_seed(n))).to(dev).contiguous()
+        head = blk[:64].cpu().numpy()
+        host_reps = 2 if n <= 256 else 1
+        for k in (50, 100, 1024):
+            ids = torch.empty(n, k, dtype=torch.int32, device=dev)
+            new = lambda: wide(blk, ids, k)
+            tk = lambda: torch.topk(blk, k, dim=1)
+            for _ in range(3):                               # warm-up: code objects, allocator
+                new()
+                t = tk()
+            torch.cuda.synchronize()
+            got = ids.cpu().numpy().astype(np.int64)
+            stable = bool((got[:64] == np.argsort(-head, axis=1, kind="stable")[:, :k]).all())
+            ti = t.indices.cpu().numpy()
+            same = float(np.mean([set(x) == set(y) for x, y in zip(got.tolist(), ti.tolist())]))
+            del t
+            t_new, t_tk, t_host, host_equal = [], [], [], True
+            for rep in range(args.reps):                     # alternate the paths on the same block
+                t_new += timed(new, 1)
+                t_tk += timed(tk, 1)
+                if rep < host_reps:
+                    ms, top = host(blk, k)
+                    t_host.append(ms)
+                    host_equal = host_equal and bool((top == got).all())
+            r = {"metric": "topk_wide", "users": n, "items": I, "k": k, "reps": args.reps,
+                 "wide_ms": stats(t_new), "torch_topk_ms": stats(t_tk),
+                 "host_ms": {"reps": host_reps, "times": t_host, "median": float(np.median(t_host))},
+                 "median_ratio_host_over_wide": float(np.median(t_host) / np.median(t_new)),
+                 "median_ratio_torch_over_wide": float(np.median(t_tk) / np.median(t_new)),
+                 "ids_equal_stable_argsort_first_64_rows": stable, "ids_equal_host_argsort": host_equal,
+                 "rows_with_torch_topk_id_sets_equal": same, "block_bytes": 4 * n * I}
+            print(json.dumps(r), flush=True)
+            out.append(r)
+        # reported only: rg_topk_rows keeps k <= 32 whatever this says
+        ids, ids_n = (torch.empty(n, 32, dtype=torch.int32, device=dev) for _ in range(2))
+        new, old = (lambda: wide(blk, ids, 32)), (lambda: narrow(blk, ids_n, 32))
+        for _ in range(3):
+            new()
+            old()
+        t_new, t_old = [], []
+        for _ in range(args.reps):
+            t_new += timed(new, 1)
+            t_old += timed(old, 1)
+        r = {"metric": "topk_wide", "users": n, "items": I, "k": 32, "reps": args.reps, "wide_ms": stats(t_new),
+             "topk_rows_ms": stats(t_old),
+             "median_ratio_wide_over_topk_rows": float(np.median(t_new) / np.median(t_old)),
+             "ids_equal": bool(torch.equal(ids, ids_n))}
+        print(json.dumps(r), flush=True)
+        out.append(r)
+        del blk, ids, ids_n
+        torch.cuda.empty_cache()
+    return out
+
+
 def main_gan_recommend(args):
     """``--metric gan_recommend``: rg_gan_generate, and rg_gan_recommend's stored and fused paths, on
     one batch at the slate evaluation's shape."""
@@ -659,7 +757,7 @@ def main_scores(args):
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--metric", choices=("scores", "mrr", "slates", "pairs", "mf_scores", "mf_topk", "item_sim",
-                                        "gan_recommend"), default="scores")
+                                        "gan_recommend", "topk_wide"), default="scores")
     ap.add_argument("--batch", type=int, default=8192)
     ap.add_argument("--users", type=int, default=None)
     ap.add_argument("--hist-len", type=int, default=128)
@@ -675,7 +773,7 @@ def main(argv=None):
         args.reps = 5 if slates or args.metric == "pairs" else 20
     return {"scores": main_scores, "mrr": main_mrr, "slates": main_slates, "pairs": main_pairs,
             "mf_scores": main_mf_scores, "mf_topk": main_mf_topk, "item_sim": main_item_sim,
-            "gan_recommend": main_gan_recommend}[args.metric](args)
+            "gan_recommend": main_gan_recommend, "topk_wide": main_topk_wide}[args.metric](args)
 
 
 if __name__ == "__main__":

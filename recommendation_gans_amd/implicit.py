@@ -94,17 +94,24 @@ def _exclude_csr_rows(blk, csr, rows):
 
 
 def _topk_block(blk, k):
-    """rg_topk_rows on a contiguous fp32 score block: its rows' k best column ids as (int32
-    [rows, k] on the device, the same on the host), range-checked before anything is indexed
-    with them."""
+    """The k best column ids of a contiguous fp32 score block's rows as (int32 [rows, k] on the
+    device, the same on the host), range-checked before anything is indexed with them:
+    rg_topk_rows for k <= 32, rg_topk_rows_wide (radix select, the same order) for
+    32 < k <= 1024."""
     from . import _lib
     n, cols = blk.shape
     out = torch.empty(n, k, dtype=torch.int32, device=blk.device)
-    _lib.check(_lib.load().rg_topk_rows(_lib.stream_handle(), _lib.ptr(blk), n, cols, cols, int(k), _lib.ptr(out)),
-               "rg_topk_rows")
+    if k <= 32:
+        name = "rg_topk_rows"
+        rc = _lib.load().rg_topk_rows(_lib.stream_handle(), _lib.ptr(blk), n, cols, cols, int(k), _lib.ptr(out))
+    else:
+        name = "rg_topk_rows_wide"
+        rc = _lib.load().rg_topk_rows_wide(_lib.stream_handle(), _lib.ptr(blk), n, cols, cols, int(k), _lib.ptr(out),
+                                           None)
+    _lib.check(rc, name)
     got = out.cpu().numpy()
     if got.size and (got.min() < 0 or got.max() >= cols):
-        raise RuntimeError("rg_topk_rows returned an item id outside the table")
+        raise RuntimeError(f"{name} returned an item id outside the table")
     return out, got
 
 
@@ -442,10 +449,14 @@ class ImplicitFactorizationModel:
         u = torch.as_tensor(np.asarray(users, dtype=np.int64), device=self._engine.device)
         return self._device_scores(u).cpu().numpy()
 
+    # the largest k of topk_users (rg_topk_rows_wide); spotlight/evaluation.py routes its @k metrics by it
+    topk_users_max = 1024
+
     def topk_users(self, users, k, exclude_csr=None):
         """The first k entries of argsort(-scores) for a block of users (evaluation.py:
-        precision/recall@k, hit ratio, MAP@k), ranked on the device by rg_topk_rows;
-        items of ``exclude_csr``'s rows rank last (the reference's FLOAT_MAX).  Returns
+        precision/recall@k, hit ratio, MAP@k), ranked on the device by rg_topk_rows, for
+        32 < k <= min(1024, num_items) by rg_topk_rows_wide (``_topk_block``); items of
+        ``exclude_csr``'s rows rank last (the reference's FLOAT_MAX).  Returns
         (len(users), k) int64 on the host."""
         ub, s = _score_block(self, users)
         _exclude_csr_rows(s, exclude_csr, ub)
@@ -468,7 +479,8 @@ class ImplicitFactorizationModel:
         one (README), so it is kept wherever it fits.  Both give the same ids and score bits; only
         ids and scores come down.  After a data-parallel fit the gathered full tables are used, as
         in ``predict``.  ValueError for an id outside the model, k < 1, k > min(32, num_items) or an
-        ``exclude`` of another shape."""
+        ``exclude`` of another shape.  The cap stays 32 here (the fused kernel's lists hold no more);
+        ``topk_users`` ranks up to 1024 ids."""
         users = np.asarray(user_ids, dtype=np.int64).reshape(-1)
         k, n, num_items = int(k), len(users), self._num_items
         if k < 1 or k > min(32, num_items):
@@ -528,7 +540,9 @@ class ImplicitFactorizationModel:
         (``mf_engine.similar_rows``: product, similarity and ranking in LDS, no (ids, items) block);
         the reciprocal norms are computed once per call.  Only ids and similarities come down.
         ValueError for an id outside [0, num_items), k < 1, k > min(32, num_items - 1) (num_items with
-        ``include_self``), an unknown ``metric`` or an unknown ``space``."""
+        ``include_self``), an unknown ``metric`` or an unknown ``space``.  The cap stays 32: the fused
+        kernel ranks in register lists, and the wide selection (rg_topk_rows_wide) reads a score block
+        that this path never builds."""
         items = np.asarray(item_ids, dtype=np.int64).reshape(-1)
         k, n, num_items = int(k), len(items), self._num_items
         if metric not in mf_engine.SIM_METRICS:

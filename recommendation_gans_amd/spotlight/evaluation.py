@@ -6,8 +6,10 @@ average precision@k, hit ratio; popularity and random baselines.  The scores of 
 block of users against every item come from one GEMM on the device
 (``model.score_users``) instead of one ``predict`` call per user; the metrics that read
 only the first k ranks (precision/recall@k, hit ratio, MAP@k) take them from the
-device top-k (``model.topk_users`` -> rg_topk_rows) when the model has one and
-k <= 32, so only users x k ids reach the host; mrr_score takes the ranks of the test items
+device top-k (``model.topk_users`` -> rg_topk_rows, above k = 32 rg_topk_rows_wide) when the model
+has one and k is within its limit -- the model's ``topk_users_max`` (1024 for
+ImplicitFactorizationModel, so the usual cut-offs 50 and 100 stay on the device), 32 for a
+model that names none -- so only users x k ids reach the host; mrr_score takes the ranks of the test items
 from the device (``model.rank_users`` -> rg_rank_rows) when the model has it;
 precision_recall_score_slates counts a device slates tensor's hits on the device (rg_slate_hits)."""
 import numpy as np
@@ -46,13 +48,17 @@ def _scored(model, test_csr, train_csr=None, block=4096):
             yield u, _row(test_csr, u), pred
 
 
-TOPK_MAX = 32
+TOPK_MAX = 32      # the device top-k limit of a model without a ``topk_users_max`` of its own
+
+
+def _device_topk(model, k):
+    return k <= getattr(model, "topk_users_max", TOPK_MAX) and hasattr(model, "topk_users")
 
 
 def _ranked(model, test_csr, train_csr=None, block=4096, k=None):
     """Yields (user, row indices, item ranking) for every test user with items; with k,
     the ranking may hold only its first k entries (the device top-k)."""
-    if k is not None and k <= TOPK_MAX and hasattr(model, "topk_users"):
+    if k is not None and _device_topk(model, k):
         for _, ub in _user_blocks(test_csr, block):
             top = model.topk_users(ub, int(k), train_csr)      # (len(ub), k) int64, host
             for r, u in enumerate(ub):
@@ -63,7 +69,7 @@ def _ranked(model, test_csr, train_csr=None, block=4096, k=None):
 
 
 def _topk_hits(model, test_csr, train_csr, k, block=4096):
-    """The device top-k path of the metrics (model.topk_users, k <= TOPK_MAX), vectorised over
+    """The device top-k path of the metrics (model.topk_users, k within _device_topk), vectorised over
     the users instead of a Python loop per user (the loop took 0.7 s per 125 k users): the users
     with test items, their top-k rankings, hits[u, j] = ranking j of user u is one of its test
     items (the rankings are distinct ids, so the count of hits in the first x ranks is the
@@ -81,10 +87,6 @@ def _topk_hits(model, test_csr, train_csr, k, block=4096):
         pos = np.minimum(np.searchsorted(keys, q), len(keys) - 1)
         hits[s:s + len(ub)] = keys[pos] == q
     return users, hits, np.diff(test_csr.indptr)[users].astype(np.int64)
-
-
-def _device_topk(model, k):
-    return k <= TOPK_MAX and hasattr(model, "topk_users")
 
 
 def mrr_score(model, test, train=None):
