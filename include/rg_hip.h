@@ -1111,6 +1111,8 @@ int rg_pool_build(uint32_t *mt_key, int32_t *mt_pos, int64_t n, int64_t num_user
  *   rg_gan_d_step  replaces CGAN.train_discriminator_iteration (CGANs.py:410-457)
  *   rg_gan_g_step  replaces CGAN.train_generator_iteration     (CGANs.py:370-408)
  *   rg_gan_generate replaces generator.forward(inference=True) (cGAN_models.py:52-62)
+ *   rg_gan_score_slates replaces discriminator.forward in eval mode on one-hot slates
+ *                  (cGAN_models.py:102-109; rg_gan_score.hip)
  * Parameters live in two flat fp32 buffers laid out by rg_gan_layout (blocks in the
  * reference's tensor order; D's layers.0.weight is split into its E history
  * columns W1E and its S*N slate columns W1S, row stride ks); optimizer state
@@ -1241,6 +1243,35 @@ int rg_gan_generate(void *stream, const rg_gan_model_t *model, void *workspace, 
 int64_t rg_gan_recommend_scratch_bytes(const rg_gan_dims_t *dims, int32_t path);
 int rg_gan_recommend(void *stream, const rg_gan_model_t *model, void *workspace, const rg_gan_batch_t *batch,
                      const float *z, int32_t flags, int32_t path, void *scratch, int32_t *slates /* [rows][S] */);
+
+/* The critic at inference: out[r] = discriminator.forward(one_hot(slates[r]), hist[r]) in eval mode
+ * (cGAN_models.py:102-109, no dropout) on the parameters as model->d stores them -- NOT clamped:
+ * the +-0.01 clamp belongs to the D iteration (CGANs.py:438-439), which clamps and then updates,
+ * so these are the values d_state_dict() returns.  Replaces feeding D a [rows][S*N] one-hot block
+ * (CGANs.py:181-198), whose first layer is a GEMM with S non-zero columns per row.  With
+ * LeakyReLU slope 0.2 throughout and the blocks of enum rg_gan_d_block:
+ *     c      = sum over l of D_EMB[hist[r][l]]                        history ids in [0, N)
+ *     u1[j]  = W1E[j] . c + sum over s of W1S[j][s*N + slates[r][s]] + B1[j]
+ *     out[r] = W4 . LeakyReLU(W3 LeakyReLU(W2 LeakyReLU(u1) + B2) + B3) + B4
+ * (line 105's LeakyReLU of the input is overwritten by line 106 and is not applied).  A history
+ * id outside [0, N) -- the padding id N included -- contributes nothing, and a slate id outside
+ * [0, N) -- the N that rg_gan_recommend writes into an empty slot included -- is an all-zero
+ * one-hot block; neither is ever used as an index.
+ * One launch (rg_gan_score.hip): a workgroup owns 16 rows, gathers their history rows and their
+ * S columns of W1S, keeps h1 and h2 in LDS and runs layers 2 and 3 on the fp32 MFMA; only out is
+ * written.  No workspace; rows is not bound by dims.batch_max; the model is only read, and
+ * model->g, every m and every v may be NULL.  slates has row stride ld >= S and its columns
+ * [S, ld) are never read.  Deterministic: every sum of a row has a fixed order that depends on
+ * the row's own data and the dims alone, so a row's score has the same bits at any position of
+ * any batch.  RG_E_ARG (rg_last_error), decided before any HIP call: a null model / model->d /
+ * hist / slates / out; dims the other rg_gan_* entries refuse, S * N beyond 31 bits, or widths
+ * whose 16-row tile exceeds a workgroup's LDS (16 (E + S + 3 H + 16) floats > 160 KiB); a
+ * model->d that is not 16-byte aligned; hist_len < 1 or > 2^31 - 129; ld < S; rows < 0; more than
+ * 16 (2^31 - 1) rows.  rows == 0 returns RG_OK without a launch. */
+int rg_gan_score_slates(void *stream, const rg_gan_model_t *model,
+                        const int32_t *hist, int32_t hist_len,      /* [rows][L], padding = N */
+                        const int32_t *slates, int64_t ld,          /* [rows][ld], ld >= S */
+                        int64_t rows, float *out /* [rows] */);
 
 /* fp32 MFMA GEMM used by the cGAN (test entry): C = A B^T with A [M][K] (a_kmajor) or
  * [K][M], B [N][K] (b_kmajor) or [K][N]; post 0 none / 1 tanh; splits > 1 uses work

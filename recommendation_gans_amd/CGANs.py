@@ -284,7 +284,7 @@ class CGAN:
             json.dump(res, fp)
         return res
 
-    def recommend(self, train_vec, exclude_history=True, distinct=True):
+    def recommend(self, train_vec, exclude_history=True, distinct=True, samples=1, return_scores=False):
         """A slate to serve for every row of ``train_vec`` (padded histories, as ``test`` takes
         them): int64 (users, slate_size) on the host.  No counterpart in the reference, whose only
         inference is each head's argmax: here the heads are taken in order, each the best item
@@ -292,14 +292,87 @@ class CGAN:
         (``distinct``); equal head outputs go to the lower id, and ``num_items`` marks a slot for
         which no item was left.  The histories go up once (``_history_chunks``, range-checked),
         the selection runs on the device (GANEngine.recommend_slates) and the slates come down in
-        one copy.  ``test`` keeps the reference's argmax slates."""
+        one copy.  ``test`` keeps the reference's argmax slates.
+
+        ``samples`` = M > 1 is discriminator-guided sampling: per history chunk and per batch of
+        ``batch_size`` rows, M noise blocks are drawn in order (``torch.rand(rows, z_dim)``), each
+        gives a candidate slate per row, the critic scores the M x rows candidates in one
+        ``score_slates`` call (the histories repeated by a copy on the device, not uploaded again), and each
+        row keeps its best-scored candidate -- equal scores: the lower sample index; a NaN score
+        loses to any number.  The selection stays on the device.  ``return_scores`` also returns
+        the kept slates' critic scores, float32 (users,) on the host (with ``samples`` = 1: the
+        score of the one slate drawn)."""
+        if isinstance(samples, bool) or not isinstance(samples, (int, np.integer)) or samples < 1:
+            raise ValueError("samples must be an integer >= 1")
         if self.engine is None:
             raise RuntimeError("call fit() first")
         out = torch.empty(len(train_vec), self.slate_size, dtype=torch.int32, device=self.device)
+        scores = torch.empty(len(train_vec), dtype=torch.float32, device=self.device) if return_scores else None
         for r0, hist in self._history_chunks(train_vec):
-            out[r0:r0 + hist.shape[0]] = self.engine.recommend_slates(hist, exclude_history=exclude_history,
-                                                                      distinct=distinct)
+            r1 = r0 + hist.shape[0]
+            if samples == 1:
+                out[r0:r1] = self.engine.recommend_slates(hist, exclude_history=exclude_history, distinct=distinct)
+                if return_scores:
+                    self.engine.score_slates(hist, out[r0:r1], out=scores[r0:r1])
+            else:
+                out[r0:r1], best = self._best_of(hist, int(samples), exclude_history, distinct)
+                if return_scores:
+                    scores[r0:r1] = best
+        if return_scores:
+            return out.cpu().to(torch.int64), scores.cpu()
         return out.cpu().to(torch.int64)
+
+    def _best_of(self, hist, M, exclude_history, distinct):
+        """``recommend``'s best of M candidates for one chunk of histories (device int32): the kept
+        slates (rows, S) int32 and their critic scores (rows,) float32, both on the device."""
+        rows, B, S, dev = hist.shape[0], self._batch_size, self.slate_size, self.device
+        cand = torch.empty(M, rows, S, dtype=torch.int32, device=dev)
+        for b0 in range(0, rows, B):
+            hb = hist[b0:b0 + B]
+            for m in range(M):
+                z = torch.rand(hb.shape[0], self.engine.Z, device=dev)
+                cand[m, b0:b0 + B] = self.engine.recommend_slates(hb, exclude_history=exclude_history,
+                                                                  distinct=distinct, z=z)
+        # the histories M times over: a copy made on the device (the entry wants contiguous rows)
+        sc = self.engine.score_slates(hist.repeat(M, 1), cand.view(M * rows, S)).view(M, rows)
+        pick = self._pick_best(sc)
+        rr = torch.arange(rows, device=dev)
+        return cand[pick, rr], sc[pick, rr]
+
+    @staticmethod
+    def _pick_best(sc):
+        """Per column of ``sc`` (samples, rows) the sample with the highest score: equal scores go
+        to the lower sample index and a NaN loses to any number, -inf included (a column of NaN
+        only: sample 0)."""
+        nan = torch.isnan(sc)
+        best = torch.where(nan, torch.full_like(sc, float("-inf")), sc).max(0).values
+        # the first sample that is a number and holds the maximum (argmax returns the first True)
+        return ((sc == best) & ~nan).to(torch.uint8).argmax(0)
+
+    def score_slates(self, train_vec, slates):
+        """The critic's eval-mode score D(one_hot(slate), history) of one slate per row of
+        ``train_vec`` (padded histories, as ``test`` takes them): float32 (users,) on the host.
+        ``slates``: an array or tensor (host or device) shaped (users, slate_size) of integral
+        values in [0, num_items]; ``num_items``, the id ``recommend`` leaves in an empty slot,
+        selects nothing.  The histories go up through ``_history_chunks`` (range-checked), the
+        slates are checked on the host, GANEngine.score_slates (rg_gan_score_slates) scores each
+        chunk and the scores come down in one copy.  The discriminator is read as stored: no
+        clamp, no dropout."""
+        if self.engine is None:
+            raise RuntimeError("call fit() first")
+        s = slates.detach().cpu().numpy() if torch.is_tensor(slates) else np.asarray(slates)
+        if s.ndim != 2 or s.shape != (len(train_vec), self.slate_size):
+            raise ValueError(f"slates must be ({len(train_vec)}, {self.slate_size}): one slate per history row")
+        if s.dtype.kind not in "iuf" or (s.dtype.kind == "f" and not np.all(s == np.floor(s))):
+            raise ValueError("slates must hold integral values")
+        if s.size and (s.min() < 0 or s.max() > self.num_items):
+            raise ValueError("slate ids must lie in [0, num_items] (num_items = an empty slot)")
+        sl = torch.from_numpy(np.ascontiguousarray(s.astype(np.int32))).to(self.device)
+        out = torch.empty(len(s), dtype=torch.float32, device=self.device)
+        for r0, hist in self._history_chunks(train_vec):
+            r1 = r0 + hist.shape[0]
+            self.engine.score_slates(hist, sl[r0:r1], out=out[r0:r1])
+        return out.cpu()
 
     def save_readable_model(self, model_save_dir, state_dict):
         fname = os.path.join(model_save_dir, "generator")

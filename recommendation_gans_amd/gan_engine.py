@@ -394,6 +394,36 @@ class GANEngine:
                                             ctypes.c_void_p(sl.data_ptr() + r0 * self.S * 4)), "rg_gan_recommend")
         return sl
 
+    def score_slates(self, hist, slates, out=None):
+        """The critic's eval-mode score of each row's slate (rg_gan_score_slates): ``hist`` device
+        int32 (rows, L) and ``slates`` device int32 (rows, >= S), both contiguous; columns of
+        ``slates`` from S on are not read.  History and slate ids outside [0, N) -- the padding
+        id N included -- select nothing and are never used as an index.  The discriminator's
+        parameters are read as stored (not clamped) and left untouched.  Any number of rows, one
+        launch, no workspace.  Returns a float32 (rows,) device tensor (``out`` when given) on
+        the current stream; no host synchronisation."""
+        for name, t in (("hist", hist), ("slates", slates)):
+            if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 2 or t.device != self.device or \
+                    not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous int32 2-d tensor on the engine's device")
+        rows, L = hist.shape
+        if slates.shape[0] != rows:
+            raise ValueError(f"hist has {rows} rows, slates {slates.shape[0]}")
+        if slates.shape[1] < self.S:
+            raise ValueError(f"slates must have at least slate_size = {self.S} columns")
+        if L < 1:
+            raise ValueError("hist must have at least one column")
+        if out is None:
+            out = torch.empty(rows, dtype=torch.float32, device=self.device)
+        elif not torch.is_tensor(out) or out.dtype != torch.float32 or out.shape != (rows,) or \
+                out.device != self.device or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 (rows,) tensor on the engine's device")
+        if rows == 0:       # an empty tensor has no pointer to hand over
+            return out
+        check(self.lib.rg_gan_score_slates(self._stream(), ctypes.byref(self._model()), ptr(hist), L, ptr(slates),
+                                           slates.shape[1], rows, ptr(out)), "rg_gan_score_slates")
+        return out
+
     def slate_hits(self, hist, tgt_ptr, tgt_idx, k, out=None):
         """Generates a slate for every row of ``hist`` (``generate_slates``) and marks, with one
         rg_slate_hits launch over all rows, which of each slate's first k items are among the
