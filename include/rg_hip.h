@@ -28,6 +28,8 @@
  *                       (the block the ranking metrics read)
  *                                                          spotlight/evaluation.py:13-60, :115-213
  *   rg_mf_topk_users    the k best items of those users, scored, excluded and ranked in LDS
+ *   rg_mf_fold_in_users rows and biases of NEW users fitted against the frozen item tables
+ *                       (the model's loss, Adam; no reference counterpart: it retrains)
  *   rg_topk_rows_wide   the first k <= 1024 entries of argsort(-scores) of a score block
  *                                                          spotlight/evaluation.py:115-213
  *   rg_item_sim_topk    the k rows of an embedding table most similar to each query row
@@ -959,6 +961,53 @@ int rg_mf_topk_users(void *stream, const float *user_w, const float *item_w,
                      int64_t num_items, const int64_t *users_dev, int64_t n_users,
                      const int64_t *exc_ptr, const int32_t *exc_idx, int32_t k, int32_t splits,
                      void *workspace_dev, int32_t *out_idx, float *out_scores);
+
+/* ------------------------------------------------------------------------------
+ * MF fold-in (rg_mf_fold.hip): fit the rows and biases of users that were not in the training
+ * set against FROZEN item tables -- no reference counterpart (the reference retrains).  One
+ * launch, no workspace; item_w [num_items][dim] and item_b [num_items] are only read.
+ *
+ * User r's history is the CSR row hist_idx[hist_ptr[r] .. hist_ptr[r + 1]) (device, int64
+ * offsets, int32 item ids; duplicates count as given, P = 0 allowed); negative j of its
+ * positive p is neg_idx[(hist_ptr[r] + p) * n_neg + j], the same at every step (neg_idx may be
+ * null iff n_neg == 0).  With s(i) = sigmoid((<w, Q_i> + b) + c_i), BilinearNet's prediction,
+ * the row's loss is spotlight/losses.py applied to that one user's pairs:
+ *   RG_LOSS_POINTWISE       -(1/P) sum_p max(log s(i_p), -100)
+ *                           - (1/(P n)) sum_{p,j} max(log(1 - s(neg_pj)), -100)
+ *                           (n_neg == 0: the first term only)
+ *   RG_LOSS_BPR             (1/(P n)) sum_{p,j} (1 - sigmoid(s(i_p) - s(neg_pj)))
+ *   RG_LOSS_HINGE           (1/(P n)) sum_{p,j} max(0, s(neg_pj) - s(i_p) + 1)
+ *   RG_LOSS_ADAPTIVE_HINGE  (1/P) sum_p max(0, max_j s(neg_pj) - s(i_p) + 1): the maximum over
+ *                           that positive's OWN n_neg negatives, equal values going to the lowest j
+ *                           (the training step's maximum over the whole batch is a quirk of the
+ *                           reference's flat shapes and means nothing for a single user)
+ * and `steps` full-batch steps of torch's Adam act on (w, b): coupled weight decay (g += wd *
+ * param), moments starting at zero, the update of opt_update (one element of torch.optim.Adam).
+ * opt->step_size / bias_correction2_sqrt are not read: step t (0-based) takes step_coef[t] =
+ * {lr / (1 - beta1^(t+1)), sqrt(1 - beta2^(t+1))}, evaluated in double on the host (device,
+ * [steps][2] fp32, 8-byte aligned).  user_w [n_users][dim] and user_b [n_users] (device) hold the
+ * start on entry and the result on return; a row with P = 0 is left exactly as it was.  loss_out
+ * (optional, [n_users]): the loss at the last step's parameters BEFORE its update (0 for P = 0).
+ *
+ * A user is owned by one group of lanes (the pair kernel's lane x float4 row layout; 64 / lanes
+ * users per wave) for all steps: w, b, the Adam moments and the step's gradient stay in
+ * registers, the item rows are gathered (L2 after the first step), the dot is reduced over the
+ * group's lanes.  A user's summation order depends on its own row alone: its output bits do not
+ * depend on its position in the call, the number of users or the other users' histories.
+ * 16-byte loads when dim is 8, 16, 32, 64, 128 or 256 and item_w and user_w are 16-byte aligned.
+ * Ids are trusted: hist_ptr must ascend and every id lie in [0, num_items).
+ * RG_E_ARG (rg_last_error names the reason, no HIP call made, nothing written) on a null item_w,
+ * item_b, hist_ptr, opt, user_w or user_b, dim outside [1, 256], num_items outside [1, INT_MAX],
+ * n_neg outside [0, 32], steps outside [0, 1024], n_users < 0, an unknown loss, n_neg == 0 with a
+ * loss other than pointwise, a null neg_idx with n_neg > 0, opt->kind other than RG_OPT_ADAM, or
+ * (with work to do) a null hist_idx or step_coef.  steps == 0 or n_users == 0: RG_OK, no launch,
+ * nothing written.
+ * ---------------------------------------------------------------------------- */
+int rg_mf_fold_in_users(void *stream, const float *item_w, const float *item_b, int32_t dim,
+                        int64_t num_items, const int64_t *hist_ptr, const int32_t *hist_idx,
+                        const int32_t *neg_idx, int32_t n_neg, int64_t n_users, int32_t loss,
+                        const rg_opt_t *opt, const float *step_coef, int32_t steps, float *user_w,
+                        float *user_b, float *loss_out);
 
 /* ------------------------------------------------------------------------------
  * Item-to-item similarity (rg_item_sim.hip): the k rows of an embedding table most similar

@@ -109,6 +109,17 @@ alternating in one process.  Device events, min / median per path, the peak devi
 saw during one call of each, the largest difference of the two results and, at 256 rows for
 information, one batch of ``CGAN.recommend`` with ``samples=8`` (eight draws, one scoring call, the
 selection) against ``samples=1``.  One JSON line per row count.
+
+    python -m recommendation_gans_amd.eval_time --metric fold_in [--items 26744] [--reps 20]
+
+times MF fold-in: ``mf_engine.fold_in_users`` (rg_mf_fold_in_users, one launch) against
+``mf_engine.fold_in_users_torch`` (a padded gather, autograd and ``torch.optim.Adam`` per step) on the
+same inputs, alternating in one process: 256 and 4096 new users against an ``--items`` x d item
+table at d in {32, 64, 128}, 100 history items each, 3 negatives per positive, 20 steps, pointwise
+loss; ids on the device going in, rows on the device coming out.  Device events, min / median per
+path, the peak device memory of one call of each, the largest difference of the two results, and
+the kernel's time against max(gathered bytes at 8 TB/s, flops at the fp32 vector peak).  One JSON
+line per shape.
 """
 import argparse
 import contextlib
@@ -577,6 +588,66 @@ def main_item_sim(args):
     return out
 
 
+def main_fold_in(args):
+    """``--metric fold_in``: mf_engine.fold_in_users (rg_mf_fold_in_users, one launch) against
+    fold_in_users_torch (padded gather, autograd, torch.optim.Adam per step) on the same inputs: new
+    users with 100 history items each, 3 negatives per positive, 20 steps, pointwise loss; ids on the
+    device going in, rows on the device coming out.  ``bound_ms``: max(gathered bytes at 8 TB/s,
+    flops at the 157.3 TFLOP/s fp32 vector peak) -- every step gathers users * 100 * 4 rows of
+    (dim + 1) floats and spends 4 * dim flops on each (the dot and the gradient accumulation)."""
+    from . import mf_engine
+    dev = torch.device("cuda:0")
+    I, hist, n_neg, steps = args.items, 100, 3, 20
+    out = []
+
+    def peak(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        fn()
+        torch.cuda.synchronize()
+        return int(torch.cuda.max_memory_allocated() - base)
+
+    for d in (32, 64, 128):
+        g = torch.Generator().manual_seed(d)
+        Q = (torch.randn(I, d, generator=g) / d ** 0.5).to(dev)
+        c = (torch.randn(I, generator=g) * 0.1).to(dev)
+        for n in (256, 4096):
+            rs = np.random.RandomState(n + d)
+            ptr = torch.arange(0, (n + 1) * hist, hist, dtype=torch.int64, device=dev)
+            idx = torch.from_numpy(rs.randint(0, I, n * hist).astype(np.int32)).to(dev)
+            neg = torch.from_numpy(rs.randint(0, I, n * hist * n_neg).astype(np.int32)).to(dev)
+            kw = dict(loss="pointwise", steps=steps, lr=0.05, weight_decay=1e-6, checked=True)
+
+            def new():
+                return mf_engine.fold_in_users(Q, c, ptr, idx, neg, n_neg, **kw)
+
+            def old():
+                return mf_engine.fold_in_users_torch(Q, c, ptr, idx, neg, n_neg, **kw)
+
+            for _ in range(3):                               # warm-up: code objects, allocator
+                a, b = new(), old()
+            torch.cuda.synchronize()
+            diff = float(max((a[0] - b[0]).abs().max(), (a[1] - b[1]).abs().max()))
+            del a, b
+            t_new, t_old = [], []
+            for _ in range(args.reps):                       # alternate the two paths
+                t_new += timed(new, 1)
+                t_old += timed(old, 1)
+            rows = n * hist * (1 + n_neg) * steps
+            bound = max(rows * (d + 1) * 4 / 8e12, rows * 4 * d / 157.3e12) * 1e3
+            r = {"metric": "fold_in", "dim": d, "users": n, "items": I, "history": hist, "n_neg": n_neg,
+                 "steps": steps, "loss": "pointwise", "reps": args.reps, "kernel_ms": stats(t_new),
+                 "torch_ms": stats(t_old), "median_ratio_torch_over_kernel": float(np.median(t_old) / np.median(t_new)),
+                 "kernel_peak_bytes": peak(new), "torch_peak_bytes": peak(old), "max_abs_diff": diff,
+                 "bound_ms": bound, "kernel_over_bound": float(np.median(t_new) / bound)}
+            print(json.dumps(r), flush=True)
+            out.append(r)
+        del Q, c
+        torch.cuda.empty_cache()
+    return out
+
+
 def main_topk_wide(args):
     """``--metric topk_wide``: rg_topk_rows_wide on one score block already on the device, against
     the host path it replaces in the @k metrics above k = 32 (the block to the host, argsort per row)
@@ -837,7 +908,7 @@ def main_scores(args):
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--metric", choices=("scores", "mrr", "slates", "pairs", "mf_scores", "mf_topk", "item_sim",
-                                        "gan_recommend", "topk_wide", "gan_score"), default="scores")
+                                        "gan_recommend", "topk_wide", "gan_score", "fold_in"), default="scores")
     ap.add_argument("--batch", type=int, default=8192)
     ap.add_argument("--users", type=int, default=None)
     ap.add_argument("--hist-len", type=int, default=128)
@@ -854,7 +925,7 @@ def main(argv=None):
     return {"scores": main_scores, "mrr": main_mrr, "slates": main_slates, "pairs": main_pairs,
             "mf_scores": main_mf_scores, "mf_topk": main_mf_topk, "item_sim": main_item_sim,
             "gan_recommend": main_gan_recommend, "topk_wide": main_topk_wide,
-            "gan_score": main_gan_score}[args.metric](args)
+            "gan_score": main_gan_score, "fold_in": main_fold_in}[args.metric](args)
 
 
 if __name__ == "__main__":

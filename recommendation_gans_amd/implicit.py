@@ -115,6 +115,35 @@ def _topk_block(blk, k):
     return out, got
 
 
+def _histories_csr(histories, num_items):
+    """New users' histories as a CSR over item ids, (indptr int64 [n + 1], indices int32): a scipy
+    sparse matrix or an Interactions with ``num_items`` columns (its rows, indices as stored), or a
+    list of id sequences (each in the order given, duplicates kept).  ValueError for another width or
+    an id outside [0, num_items)."""
+    if hasattr(histories, "tocsr"):
+        csr = histories.tocsr()
+        if csr.shape[1] != num_items:
+            raise ValueError(f"histories have {csr.shape[1]} columns, the model {num_items} items")
+        ptr, idx = csr.indptr.astype(np.int64), csr.indices.astype(np.int64)
+    else:
+        rows = [np.asarray(r, dtype=np.int64).reshape(-1) for r in histories]
+        ptr = np.zeros(len(rows) + 1, dtype=np.int64)
+        np.cumsum([len(r) for r in rows], out=ptr[1:])
+        idx = np.concatenate(rows) if rows else np.zeros(0, dtype=np.int64)
+    if len(idx) and (idx.min() < 0 or idx.max() >= num_items):
+        raise ValueError("history item id outside [0, num_items)")
+    return ptr, idx.astype(np.int32)
+
+
+def _fold_negatives(nnz, n_neg, num_items, random_state, device=None):
+    """The fold-in's negatives, drawn once: ``random_state.randint(0, num_items, nnz * n_neg)`` --
+    uniform over the items, so one may coincide with a positive, as in the reference -- through the
+    device sampler (``sample_items(..., device=)``: NumPy's values, the RandomState advanced as NumPy
+    advances it); entry e's negative j is element e * n_neg + j."""
+    from .spotlight.sampling import sample_items
+    return sample_items(None, None, num_items, (int(nnz) * int(n_neg),), random_state=random_state, device=device)
+
+
 def _score_block_fits(n, num_items, device):
     """Whether recommend may build the (n, num_items) fp32 score block: twice its size within the
     device's free memory (the driver's free bytes plus what torch's allocator holds unused).  The
@@ -519,6 +548,88 @@ class ImplicitFactorizationModel:
             ids[s:s + len(ub)] = got
             if return_scores:
                 scores[s:s + len(ub)] = torch.gather(blk, 1, out.to(torch.int64)).cpu().numpy()
+        return (ids, scores) if return_scores else ids
+
+    def _fold_in_device(self, histories, steps, lr, n_neg, l2, random_state, return_loss):
+        """``fold_in_users`` up to the device results: (indptr, indices, (W, b[, loss]) on the device)."""
+        if not self._initialized:
+            raise RuntimeError("fold_in_users needs a fitted model")
+        if self._kind != "mf":
+            raise NotImplementedError("fold-in is implemented for the matrix-factorization model (BilinearNet)")
+        ptr, idx = _histories_csr(histories, self._num_items)
+        loss = "pointwise" if self._no_negatives else _LOSS_MAP[self._loss]
+        if n_neg is None:
+            n_neg = 0 if self._no_negatives else self._num_negative_samples
+        o = self._opt
+        dev = self._engine.device
+        rs = random_state if random_state is not None else self._random_state
+        neg = _fold_negatives(len(idx), n_neg, self._num_items, rs, dev) if n_neg and len(idx) else None
+        _, item_w, _, item_b = self._tables()
+        out = mf_engine.fold_in_users(item_w, item_b, ptr, idx, neg, n_neg, loss=loss, steps=steps,
+                                      lr=o["lr"] if lr is None else lr,
+                                      weight_decay=o["weight_decay"] if l2 is None else l2,
+                                      betas=o.get("betas", (0.9, 0.999)), eps=o.get("eps", 1e-8),
+                                      return_loss=return_loss, checked=True)
+        return ptr, idx, out
+
+    def fold_in_users(self, histories, steps=20, lr=None, n_neg=None, l2=None, random_state=None,
+                      return_loss=False):
+        """Factors and biases for users that were NOT in the training set, from their histories alone
+        (fold-in): the item tables stay frozen and each new user's row and bias are fitted with the
+        model's own loss by ``steps`` full-batch Adam steps from zero, all users in one launch
+        (``mf_engine.fold_in_users``, rg_mf_fold_in_users).  Returns host arrays ``(factors [n, dim],
+        biases [n])`` float32, with ``return_loss`` also the per-user loss at the last step.
+
+        ``histories``: a scipy sparse matrix or an Interactions with ``num_items`` columns (one row
+        per new user), or a list of item-id sequences; a user with an empty history keeps the zero
+        row.  ``lr``, ``n_neg`` and ``l2`` default to the model's learning rate, negatives per
+        positive and weight decay (Adam's betas and eps are the model's when it trained with Adam).
+        The negatives are drawn once, uniformly over the items (they may coincide with a positive, as
+        in the reference), from ``random_state`` or else the model's own RandomState, which the draw
+        advances: an equally seeded RandomState reproduces the call.  The adaptive hinge ('bpr' and
+        'adaptive_hinge') takes the maximum over each positive's own negatives.  After a
+        data-parallel fit the gathered full tables are used, as in ``predict``.  MF only: the NCF and
+        NeuMF models raise NotImplementedError."""
+        out = self._fold_in_device(histories, steps, lr, n_neg, l2, random_state, return_loss)[2]
+        return tuple(t.cpu().numpy() for t in out)
+
+    def recommend_for_histories(self, histories, k=10, exclude_history=True, return_scores=False, **fold_kwargs):
+        """``recommend`` for users the model has never seen: their rows are folded in from
+        ``histories`` (``fold_in_users``; ``fold_kwargs`` are its ``steps``, ``lr``, ``n_neg``, ``l2``
+        and ``random_state``) and ranked like known users -- ``(len(histories), k)`` int64 item ids on
+        the host in rank order (higher score first, then the lower item id), with ``return_scores``
+        also their float32 scores.  ``exclude_history`` leaves each row's own history out: those
+        items have the score -inf and are only returned, by id, to a row with fewer than k other
+        items.  One fold-in for all rows, then 4096 rows at a time: ``mf_engine.score_users_block``
+        with the folded rows as the user table, -inf over the block's histories, rg_topk_rows, and the
+        scores gathered from the block at the returned ids.  ValueError for k < 1 or
+        k > min(32, num_items), as ``recommend``."""
+        k, num_items = int(k), self._num_items
+        if self._initialized and (k < 1 or k > min(32, num_items)):
+            raise ValueError("k must be in [1, min(32, num_items)]")
+        extra = set(fold_kwargs) - {"steps", "lr", "n_neg", "l2", "random_state"}
+        if extra:
+            raise TypeError(f"recommend_for_histories: unexpected arguments {sorted(extra)}")
+        args = dict(steps=20, lr=None, n_neg=None, l2=None, random_state=None)
+        args.update(fold_kwargs)
+        ptr, idx, (W, b) = self._fold_in_device(histories, return_loss=False, **args)
+        n = len(ptr) - 1
+        ids = np.empty((n, k), dtype=np.int64)
+        scores = np.empty((n, k), dtype=np.float32)
+        dev = self._engine.device
+        _, item_w, _, item_b = self._tables()
+        for s in range(0, n, 4096):
+            e = min(s + 4096, n)
+            blk = mf_engine.score_users_block(W[s:e], item_w, b[s:e], item_b, torch.arange(e - s, device=dev),
+                                              checked=True)
+            if exclude_history and ptr[e] > ptr[s]:
+                r = np.repeat(np.arange(e - s), np.diff(ptr[s:e + 1]))
+                blk[torch.as_tensor(r, device=dev),
+                    torch.as_tensor(idx[ptr[s]:ptr[e]].astype(np.int64), device=dev)] = float("-inf")
+            out, got = _topk_block(blk, k)
+            ids[s:e] = got
+            if return_scores:
+                scores[s:e] = torch.gather(blk, 1, out.to(torch.int64)).cpu().numpy()
         return (ids, scores) if return_scores else ids
 
     def _item_table(self, space):

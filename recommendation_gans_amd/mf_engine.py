@@ -269,6 +269,194 @@ def similar_rows(table, queries, k, metric="cosine", exclude_self=True, rnorm=No
     return ids, sims
 
 
+FOLD_LOSSES = ("pointwise", "bpr", "hinge", "adaptive_hinge")
+FOLD_MAX_NEG, FOLD_MAX_STEPS = 32, 1024     # rg_mf_fold_in_users' ranges
+
+
+def adam_step_coef(steps, lr, betas):
+    """(steps, 2) float64: torch.optim.Adam's per-step scalars of steps 1..steps, evaluated in double
+    as its Python code does -- step_size = lr / (1 - beta1^t), bias_correction2_sqrt =
+    sqrt(1 - beta2^t) (what rg_opt_t carries for one step)."""
+    out = np.empty((int(steps), 2), dtype=np.float64)
+    for t in range(1, int(steps) + 1):
+        out[t - 1, 0] = float(lr) / (1.0 - float(betas[0]) ** t)
+        out[t - 1, 1] = (1.0 - float(betas[1]) ** t) ** 0.5
+    return out
+
+
+def _fold_args(item_w, item_b, hist_ptr, hist_idx, neg_idx, n_neg, loss, steps, init, checked, what):
+    """The argument checks both fold-in paths share (ValueError, before anything touches a device
+    kernel): returns (hist_ptr, hist_idx, neg_idx [nnz, n_neg], n, dim) with the id
+    arrays flat integer tensors, in the dtypes and on the devices they came in."""
+    if not (torch.is_tensor(item_w) and torch.is_tensor(item_b) and item_w.dtype == item_b.dtype and
+            item_w.dtype in (torch.float32, torch.float64)):
+        raise ValueError(f"{what}: the item tables must be floating-point tensors of one dtype")
+    if item_w.dim() != 2 or item_w.shape[0] < 1 or item_b.numel() != item_w.shape[0]:
+        raise ValueError(f"{what}: item_w must be (num_items >= 1, dim) and item_b hold one value per item")
+    num_items, dim = int(item_w.shape[0]), int(item_w.shape[1])
+    if dim < 1 or dim > 256:
+        raise ValueError(f"{what}: dim must be in [1, 256]")
+    if loss not in FOLD_LOSSES:
+        raise ValueError(f"{what}: unknown loss {loss!r}: one of {FOLD_LOSSES}")
+    n_neg, steps = int(n_neg), int(steps)
+    if n_neg < 0 or n_neg > FOLD_MAX_NEG:
+        raise ValueError(f"{what}: n_neg must be in [0, {FOLD_MAX_NEG}]")
+    if n_neg == 0 and loss != "pointwise":
+        raise ValueError(f"{what}: the pairwise losses need n_neg >= 1")
+    if steps < 0 or steps > FOLD_MAX_STEPS:
+        raise ValueError(f"{what}: steps must be in [0, {FOLD_MAX_STEPS}]")
+    ints = (torch.int32, torch.int64)
+    hist_ptr, hist_idx = torch.as_tensor(hist_ptr), torch.as_tensor(hist_idx)
+    neg_idx = torch.as_tensor(neg_idx) if neg_idx is not None else torch.zeros(0, dtype=torch.int32)
+    if hist_ptr.dtype not in ints or hist_idx.dtype not in ints or neg_idx.dtype not in ints:
+        raise ValueError(f"{what}: hist_ptr, hist_idx and neg_idx must be int32 or int64")
+    hist_ptr, hist_idx, neg_idx = hist_ptr.reshape(-1), hist_idx.reshape(-1), neg_idx.reshape(-1)
+    if hist_ptr.numel() < 1:
+        raise ValueError(f"{what}: hist_ptr must have n_users + 1 entries")
+    n, nnz = int(hist_ptr.numel()) - 1, int(hist_idx.numel())
+    if neg_idx.numel() != nnz * n_neg:
+        raise ValueError(f"{what}: neg_idx must hold n_neg ids per history entry")
+    if not checked:
+        bad = (hist_ptr[0] != 0) | (hist_ptr[-1] != nnz) | (hist_ptr[1:] < hist_ptr[:-1]).any()
+        if bool(bad):
+            raise ValueError(f"{what}: hist_ptr must ascend from 0 to len(hist_idx)")
+        for name, ids in (("hist_idx", hist_idx), ("neg_idx", neg_idx)):
+            if ids.numel():
+                lo, hi = torch.stack(ids.aminmax()).tolist()
+                if lo < 0 or hi >= num_items:
+                    raise ValueError(f"{what}: {name} holds an item id outside [0, num_items)")
+    if init is not None:
+        if not (isinstance(init, (tuple, list)) and len(init) == 2 and torch.is_tensor(init[0]) and
+                torch.is_tensor(init[1]) and tuple(init[0].shape) == (n, dim) and init[1].numel() == n):
+            raise ValueError(f"{what}: init must be (W [n_users, dim], b [n_users]) tensors")
+    return hist_ptr, hist_idx, neg_idx.reshape(nnz, n_neg), n, dim
+
+
+def fold_in_users(item_w, item_b, hist_ptr, hist_idx, neg_idx, n_neg, *, loss, steps, lr, weight_decay=0.0,
+                  betas=(0.9, 0.999), eps=1e-8, init=None, return_loss=False, checked=False):
+    """Fit the rows of NEW users against the frozen item tables (fold-in): ``(W [n, dim], b [n])``
+    float32 on the tables' device, with ``return_loss`` also ``loss [n]``, the loss at the last
+    step's parameters before its update.  One launch (rg_mf_fold_in_users): a user's row, bias and
+    Adam moments stay in registers for all ``steps``; the item tables are only read.
+
+    User r's history is the CSR row ``hist_idx[hist_ptr[r]:hist_ptr[r + 1]]`` (duplicates count as
+    given, an empty row is left at its start), negative j of history entry e is ``neg_idx[e * n_neg
+    + j]`` -- the same draws at every step.  ``loss``: one of ``FOLD_LOSSES``, spotlight/losses.py
+    on that one user's pairs with prediction sigmoid(<w, Q_i> + b + c_i); the adaptive hinge takes
+    the maximum over each positive's own ``n_neg`` negatives (the training step's maximum over the
+    whole batch is a quirk of the reference's flat shapes and means nothing for one user).
+    ``steps`` full-batch steps of torch's Adam (``lr``, ``betas``, ``eps``, coupled
+    ``weight_decay``) from ``init = (W0, b0)``, zeros by default.
+
+    ValueError for tables that are not contiguous float32 on one CUDA device (there is no torch
+    fall-back), dim outside [1, 256], n_neg outside [0, 32] (0 only with the pointwise loss), steps
+    outside [0, 1024], index arrays that are not integers, a ``hist_ptr`` that does not ascend from
+    0 to len(hist_idx), and an item id outside [0, num_items) (one download of the ids' bounds;
+    ``checked=True``: the caller has checked pointers and ids already)."""
+    what = "fold_in_users"
+    if not (torch.is_tensor(item_w) and torch.is_tensor(item_b) and item_w.dtype == torch.float32 and
+            item_b.dtype == torch.float32):
+        raise ValueError(f"{what}: the item tables must be float32 tensors")
+    hp, hi, ni, n, dim = _fold_args(item_w, item_b, hist_ptr, hist_idx, neg_idx, n_neg, loss, steps, init, checked,
+                                    what)
+    n_neg, steps = int(n_neg), int(steps)
+    if not (item_w.is_cuda and item_w.dtype == torch.float32 and item_w.is_contiguous() and item_b.is_contiguous()
+            and item_b.device == item_w.device):
+        raise ValueError(f"{what} needs contiguous float32 item tables on one CUDA device")
+    dev, num_items = item_w.device, int(item_w.shape[0])
+    if init is None:
+        W = torch.zeros(n, dim, dtype=torch.float32, device=dev)
+        b = torch.zeros(n, dtype=torch.float32, device=dev)
+    else:
+        W = init[0].detach().to(dev, torch.float32, copy=True).contiguous()
+        b = init[1].detach().to(dev, torch.float32, copy=True).reshape(-1).contiguous()
+    out_loss = torch.zeros(n, dtype=torch.float32, device=dev) if return_loss else None
+    if n and steps and hi.numel():
+        hp = hp.to(dev, torch.int64).contiguous()
+        hi32 = hi.to(dev, torch.int32).contiguous()
+        ni32 = ni.to(dev, torch.int32).contiguous() if n_neg else None
+        coef = torch.from_numpy(adam_step_coef(steps, lr, betas).astype(np.float32)).to(dev)
+        o = _lib.Opt()
+        o.kind = OPT_KINDS["adam"]
+        o.lr, o.beta1, o.beta2, o.eps, o.weight_decay = lr, betas[0], betas[1], eps, weight_decay
+        o.one_minus_beta1, o.one_minus_beta2 = 1 - betas[0], 1 - betas[1]
+        with torch.cuda.device(dev):
+            check(_lib.load().rg_mf_fold_in_users(_lib.stream_handle(), ptr(item_w), ptr(item_b), dim, num_items,
+                                                  ptr(hp), ptr(hi32), ptr(ni32), n_neg, n, LOSS_KINDS[loss],
+                                                  ctypes.byref(o), ptr(coef), steps, ptr(W), ptr(b), ptr(out_loss)),
+                  "rg_mf_fold_in_users")
+    return (W, b, out_loss) if return_loss else (W, b)
+
+
+def fold_row_losses(loss, sp, sn, mask, P, n_neg):
+    """Per-row fold-in losses from padded predictions: ``sp`` (n, L) the positives', ``sn`` (n, L,
+    n_neg) their negatives', ``mask`` (n, L) True at real entries, ``P`` (n,) the row lengths as
+    floats (an empty row's loss is 0)."""
+    Pc = P.clamp(min=1.0)
+    zero = sp.new_zeros(())
+    if loss == "pointwise":
+        out = -torch.where(mask, torch.clamp(torch.log(sp), min=-100.0), zero).sum(1) / Pc
+        if n_neg:
+            neg = torch.where(mask[:, :, None], torch.clamp(torch.log(1.0 - sn), min=-100.0), zero)
+            out = out - neg.sum((1, 2)) / (Pc * n_neg)
+        return out
+    if loss == "bpr":
+        term = 1.0 - torch.sigmoid(sp[:, :, None] - sn)
+    elif loss == "hinge":
+        term = torch.clamp(sn - sp[:, :, None] + 1.0, min=0.0)
+    else:
+        return torch.where(mask, torch.clamp(sn.max(dim=2).values - sp + 1.0, min=0.0), zero).sum(1) / Pc
+    return torch.where(mask[:, :, None], term, zero).sum((1, 2)) / (Pc * n_neg)
+
+
+def fold_in_users_torch(item_w, item_b, hist_ptr, hist_idx, neg_idx, n_neg, *, loss, steps, lr, weight_decay=0.0,
+                        betas=(0.9, 0.999), eps=1e-8, init=None, return_loss=False, checked=False):
+    """``fold_in_users`` as the chain of torch ops it replaces, on the tables' device and in their
+    dtype: the histories padded to the longest row, one (n, L (1 + n_neg), dim) gather per step,
+    autograd on the summed per-row losses and ``torch.optim.Adam`` on an (n, dim) and an (n,)
+    parameter.  Per-row losses and an elementwise optimizer keep the rows independent; an empty row
+    is put back to its start.  The timing baseline of the kernel, and in float64 on the CPU the
+    reference of its tests."""
+    hp, hi, ni, n, dim = _fold_args(item_w, item_b, hist_ptr, hist_idx, neg_idx, n_neg, loss, steps, init, checked,
+                                    "fold_in_users_torch")
+    n_neg, steps = int(n_neg), int(steps)
+    dev, dt = item_w.device, item_w.dtype
+    Q, c = item_w.detach(), item_b.detach().reshape(-1)
+    if init is None:
+        W0, b0 = torch.zeros(n, dim, dtype=dt, device=dev), torch.zeros(n, dtype=dt, device=dev)
+    else:
+        W0 = init[0].detach().to(dev, dt, copy=True)
+        b0 = init[1].detach().to(dev, dt, copy=True).reshape(-1)
+    hp, hi, ni = hp.to(dev, torch.int64), hi.to(dev, torch.int64), ni.to(dev, torch.int64)
+    lens = hp[1:] - hp[:-1]
+    L = int(lens.max()) if n else 0
+    last = torch.zeros(n, dtype=dt, device=dev)
+    if n == 0 or steps == 0 or L == 0:
+        return (W0, b0, last) if return_loss else (W0, b0)
+    col = torch.arange(L, device=dev)
+    mask = col[None, :] < lens[:, None]
+    src = (hp[:-1, None] + col[None, :]).clamp(max=int(hi.numel()) - 1)
+    pos = torch.where(mask, hi[src], torch.zeros((), dtype=torch.int64, device=dev))
+    neg = torch.where(mask[:, :, None], ni[src], torch.zeros((), dtype=torch.int64, device=dev))
+    W, b = W0.clone().requires_grad_(True), b0.clone().requires_grad_(True)
+    opt = torch.optim.Adam([W, b], lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
+    P = lens.to(dt)
+    for t in range(steps):
+        opt.zero_grad(set_to_none=True)
+        sp = torch.sigmoid(torch.einsum("nd,nld->nl", W, Q[pos]) + b[:, None] + c[pos])
+        sn = torch.sigmoid(torch.einsum("nd,nlkd->nlk", W, Q[neg]) + b[:, None, None] + c[neg])
+        rows = fold_row_losses(loss, sp, sn, mask, P, n_neg)
+        if t == steps - 1:
+            last = rows.detach().clone()
+        rows.sum().backward()
+        opt.step()
+    W, b = W.detach(), b.detach()
+    empty = lens == 0
+    W[empty] = W0[empty]
+    b[empty] = b0[empty]
+    return (W, b, last) if return_loss else (W, b)
+
+
 MFPlan = namedtuple("MFPlan", "perm pos_slot item_slot_off n_planned", defaults=(None,))
 
 

@@ -1,0 +1,254 @@
+"""rg_mf_fold_in_users on the GPU: parity with the float64 reference inside twice the error of a
+float32 evaluation of the same formulas (E32, tests/fold_in_common.py), bit invariance of a user's
+result against its place in the call, the identity cases, descent, the model-level calls, and the
+entry's refusals.  300 items; every case in a few seconds.
+
+The parity bound is measured, not picked: the numpy restatement runs in float32 with the positives
+summed forward, reversed and pairwise, E32 is the largest deviation of those three from float64, and
+the kernel -- one more ordering of the same sums, with fused multiply-adds and the device's exp /
+log -- must stay within 2 x E32.  Both figures are printed per case.  Elements whose float64 gradient
+cancels below 1e-5 of its sum of |terms| at some step (Adam turns such a gradient's sign
+into +-lr), and rows where an adaptive hinge's two highest negatives (of different items) are equal
+to float32, are left out: at most 1 % of a case (checked without a GPU in test_fold_in_cpu.py).
+"""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from recommendation_gans_amd import _lib, mf_engine
+from tests import fold_in_common as fc
+from tests.ncf_infer_common import make_model
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+
+
+def run(case, loss, steps, wd, rows=None, return_loss=True):
+    """The kernel on ``case`` (or on its ``rows``, in that order, as a call of their own): host arrays."""
+    ptr, idx, neg, k = case["ptr"], case["idx"], case["neg"].reshape(len(case["idx"]), case["n_neg"]), case["n_neg"]
+    W0, b0 = case["W0"], case["b0"]
+    if rows is not None:
+        rows = np.asarray(rows)
+        lens = np.diff(ptr)[rows]
+        take = np.concatenate([np.arange(ptr[r], ptr[r + 1]) for r in rows] + [np.zeros(0, np.int64)]).astype(np.int64)
+        ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        idx, neg, W0, b0 = idx[take], neg[take], W0[rows], b0[rows]
+    t = torch.from_numpy
+    out = mf_engine.fold_in_users(t(case["Q"]).to(DEV), t(case["c"]).to(DEV), t(ptr), t(np.ascontiguousarray(idx)),
+                                  t(np.ascontiguousarray(neg).reshape(-1)), k, loss=loss, steps=steps, lr=fc.LR,
+                                  weight_decay=wd, betas=fc.BETAS, eps=fc.EPS,
+                                  init=(t(np.ascontiguousarray(W0)), t(np.ascontiguousarray(b0))),
+                                  return_loss=return_loss)
+    return tuple(x.cpu().numpy() for x in out)
+
+
+@pytest.mark.parametrize("i", range(len(fc.CASES)), ids=fc.CASE_IDS)
+def test_parity_with_the_float64_reference_within_twice_the_float32_error(i):
+    d = fc.case_data(i)
+    case = d["case"]
+    W, b, lv = run(case, d["loss"], d["steps"], d["wd"])
+    assert W.dtype == b.dtype == lv.dtype == np.float32
+    dev = fc.deviation(W, b, d["ref"][:2], d["keep_W"], d["keep_b"])
+    dev_loss = float(np.abs(lv.astype(np.float64) - d["ref"][2])[d["row_ok"]].max(initial=0.0))
+    print(f"\ncase {fc.CASE_IDS[i]}: kernel {dev:.3e} E32 {d['e32']:.3e} ratio {dev / d['e32']:.2f} | "
+          f"loss kernel {dev_loss:.3e} E32 {d['e32_loss']:.3e} ratio {dev_loss / d['e32_loss']:.2f} | "
+          f"left out {d['left_out']:.4f}")
+    empty = np.diff(case["ptr"]) == 0
+    assert W[empty].tobytes() == case["W0"][empty].tobytes() and b[empty].tobytes() == case["b0"][empty].tobytes()
+    assert (lv[empty] == 0).all()
+    assert np.isfinite(W).all() and np.isfinite(b).all() and np.isfinite(lv).all()
+    assert dev <= 2 * d["e32"]
+    assert dev_loss <= 2 * d["e32_loss"]
+
+
+@pytest.mark.parametrize("dim, n_neg, loss", [(16, 3, "pointwise"), (65, 5, "adaptive_hinge"), (128, 1, "bpr")])
+def test_a_users_bits_do_not_depend_on_its_place_in_the_call(dim, n_neg, loss):
+    case = fc.make_case(dim, 130, n_neg, seed=3, init="random")
+    steps, wd = 8, 1e-3
+    full = run(case, loss, steps, wd)
+    n = case["users"]
+    # every row as a call of its own
+    for r in range(n):
+        one = run(case, loss, steps, wd, rows=[r])
+        for a, o in zip(full, one):
+            assert a[r].tobytes() == o[0].tobytes(), f"row {r} alone"
+    # the users in reversed order
+    rev = run(case, loss, steps, wd, rows=np.arange(n)[::-1])
+    for a, o in zip(full, rev):
+        assert a.tobytes() == np.ascontiguousarray(o[::-1]).tobytes()
+    # every third user kept, the others' histories (and lengths) replaced
+    keep = np.arange(0, n, 3)
+    lens = np.diff(case["ptr"]).copy()
+    rs = np.random.RandomState(9)
+    other = np.setdiff1d(np.arange(n), keep)
+    lens[other] = rs.randint(0, 90, len(other))
+    changed = fc.make_case(dim, n, n_neg, seed=4, init="random", lens=lens)
+    changed["Q"], changed["c"] = case["Q"], case["c"]
+    k = n_neg
+    neg_c, neg_o = changed["neg"].reshape(-1, k), case["neg"].reshape(-1, k)
+    for r in keep:
+        changed["idx"][changed["ptr"][r]:changed["ptr"][r + 1]] = case["idx"][case["ptr"][r]:case["ptr"][r + 1]]
+        neg_c[changed["ptr"][r]:changed["ptr"][r + 1]] = neg_o[case["ptr"][r]:case["ptr"][r + 1]]
+        changed["W0"][r], changed["b0"][r] = case["W0"][r], case["b0"][r]
+    changed["neg"] = neg_c.reshape(-1)
+    got = run(changed, loss, steps, wd)
+    for a, o in zip(full, got):
+        assert a[keep].tobytes() == o[keep].tobytes()
+
+
+def test_zero_steps_and_empty_rows_return_the_start_and_the_tables_are_only_read():
+    case = fc.make_case(64, 130, 3, seed=5, init="random")
+    Q, c = torch.from_numpy(case["Q"]).to(DEV), torch.from_numpy(case["c"]).to(DEV)
+    before = (Q.cpu().numpy().tobytes(), c.cpu().numpy().tobytes())
+    t = torch.from_numpy
+    init = (t(case["W0"]), t(case["b0"]))
+    for steps in (0, 8):
+        W, b, lv = mf_engine.fold_in_users(Q, c, t(case["ptr"]), t(case["idx"]), t(case["neg"]), 3, loss="hinge",
+                                           steps=steps, lr=fc.LR, weight_decay=1e-3, init=init, return_loss=True)
+        W, b = W.cpu().numpy(), b.cpu().numpy()
+        same = np.ones(130, bool) if steps == 0 else np.diff(case["ptr"]) == 0
+        assert same.any()
+        assert W[same].tobytes() == case["W0"][same].tobytes() and b[same].tobytes() == case["b0"][same].tobytes()
+        if steps:
+            assert (W[~same] != case["W0"][~same]).any(axis=1).all()
+    assert (Q.cpu().numpy().tobytes(), c.cpu().numpy().tobytes()) == before
+    # the default start is zero, and no users is an empty result
+    W, b = mf_engine.fold_in_users(Q, c, t(case["ptr"]), t(case["idx"]), t(case["neg"]), 3, loss="hinge", steps=0,
+                                   lr=fc.LR)
+    assert not W.any() and not b.any() and W.shape == (130, 64) and b.shape == (130,)
+    W, b = mf_engine.fold_in_users(Q, c, np.zeros(1, np.int64), np.zeros(0, np.int32), None, 0, loss="pointwise",
+                                   steps=3, lr=fc.LR)
+    assert W.shape == (0, 64) and b.shape == (0,)
+
+
+@pytest.mark.parametrize("loss", mf_engine.FOLD_LOSSES)
+def test_the_float64_loss_of_the_returned_rows_is_below_the_loss_at_zero(loss):
+    case = fc.make_case(16, 130, 3, seed=6)
+    W, b = run(case, loss, 8, 0.0, return_loss=False)
+    live = np.diff(case["ptr"]) > 0
+    at_zero = fc.loss64(case, loss, case["W0"], case["b0"])
+    after = fc.loss64(case, loss, W, b)
+    assert (after[live] < at_zero[live]).all()
+
+
+def _histories(I, n, seed):
+    rs = np.random.RandomState(seed)
+    return [rs.choice(I, size=rs.randint(0, 40), replace=False) for _ in range(n)]
+
+
+def test_model_fold_in_is_reproducible_and_recommend_for_histories_is_its_composition(tmp_path, monkeypatch):
+    from recommendation_gans_amd import implicit
+    model, train, test = make_model("mf", tmp_path, monkeypatch, U=75, I=300, n_test=100)
+    model.fit(train, test)
+    I = model._num_items
+    hist = _histories(I, 37, 2)
+    hist[5] = np.zeros(0, np.int64)
+    a = model.fold_in_users(hist, steps=8, random_state=np.random.RandomState(5))
+    b = model.fold_in_users(hist, steps=8, random_state=np.random.RandomState(5))
+    c = model.fold_in_users(hist, steps=8, random_state=np.random.RandomState(6))
+    assert a[0].shape == (37, model._embedding_dim) and a[1].shape == (37,) and a[0].dtype == np.float32
+    assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
+    assert a[0].tobytes() != c[0].tobytes()
+    assert not a[0][5].any() and a[1][5] == 0                          # no history: the zero row
+    # the model's own RandomState is the default source, and the draw advances it
+    st = model._random_state.get_state()
+    d = model.fold_in_users(hist, steps=8)
+    rs = np.random.RandomState()
+    rs.set_state(st)
+    e = model.fold_in_users(hist, steps=8, random_state=rs)
+    assert d[0].tobytes() == e[0].tobytes()
+    assert model._random_state.randint(0, 1 << 30) == rs.randint(0, 1 << 30)
+    # the sparse form is the same call
+    ptr, idx = implicit._histories_csr(hist, I)
+    import scipy.sparse as sp
+    mat = sp.csr_matrix((np.ones(len(idx), np.float32), idx, ptr), shape=(37, I))
+    f = model.fold_in_users(mat, steps=8, random_state=np.random.RandomState(5))
+    assert f[0].tobytes() == a[0].tobytes() and f[1].tobytes() == a[1].tobytes()
+    W, bias, lv = model.fold_in_users(hist, steps=8, random_state=np.random.RandomState(5), return_loss=True)
+    assert W.tobytes() == a[0].tobytes() and lv.shape == (37,) and np.isfinite(lv).all()
+
+    # recommend_for_histories = fold-in, score block, -inf over the history, rg_topk_rows, gather
+    _, item_w, _, item_b = model._tables()
+    for k in (1, 10, 32):
+        ids, sc = model.recommend_for_histories(hist, k, return_scores=True, steps=8,
+                                                random_state=np.random.RandomState(5))
+        assert ids.dtype == np.int64 and sc.dtype == np.float32 and ids.shape == sc.shape == (37, k)
+        Wd, bd = torch.from_numpy(a[0]).to(DEV), torch.from_numpy(a[1]).to(DEV)
+        blk = mf_engine.score_users_block(Wd, item_w, bd, item_b, torch.arange(37, device=DEV))
+        r = np.repeat(np.arange(37), np.diff(ptr))
+        blk[torch.as_tensor(r, device=DEV), torch.as_tensor(idx.astype(np.int64), device=DEV)] = float("-inf")
+        out, got = implicit._topk_block(blk, k)
+        assert (ids == got).all()
+        assert sc.tobytes() == torch.gather(blk, 1, out.to(torch.int64)).cpu().numpy().tobytes()
+        for row in range(37):                                   # I - len(history) >= k other items everywhere
+            assert not np.isin(ids[row], hist[row]).any()
+        plain = model.recommend_for_histories(hist, k, exclude_history=False, steps=8,
+                                              random_state=np.random.RandomState(5))
+        full = mf_engine.score_users_block(Wd, item_w, bd, item_b, torch.arange(37, device=DEV)).cpu().numpy()
+        assert (plain == np.argsort(-full, axis=1, kind="stable")[:, :k]).all()
+    for bad in (0, 33):
+        with pytest.raises(ValueError):
+            model.recommend_for_histories(hist, bad)
+    with pytest.raises(ValueError):
+        model.fold_in_users([[0, I]])
+
+
+@pytest.mark.parametrize("kind", ["ncf", "neumf"])
+def test_fold_in_is_mf_only(kind, tmp_path, monkeypatch):
+    model, _, _ = make_model(kind, tmp_path, monkeypatch, U=20, I=50, n_test=10)
+    with pytest.raises(NotImplementedError):
+        model.fold_in_users([[1, 2, 3]])
+    with pytest.raises(NotImplementedError):
+        model.recommend_for_histories([[1, 2, 3]], 5)
+
+
+def test_the_device_sampler_draws_numpys_negatives():
+    from recommendation_gans_amd.implicit import _fold_negatives
+    a, b = np.random.RandomState(77), np.random.RandomState(77)
+    got = _fold_negatives(41, 3, 300, a, torch.device(DEV))
+    assert got.is_cuda and (got.cpu().numpy() == b.randint(0, 300, 41 * 3)).all()
+    assert a.randint(0, 1 << 30) == b.randint(0, 1 << 30)
+
+
+def test_the_entry_refuses_out_of_range_arguments_without_a_launch():
+    lib = _lib.load()
+    case = fc.make_case(8, 3, 2, lens=[2, 0, 3], init="random")
+    t = torch.from_numpy
+    Q, c = t(case["Q"]).to(DEV), t(case["c"]).to(DEV)
+    ptr, idx, neg = t(case["ptr"]).to(DEV), t(case["idx"]).to(DEV), t(case["neg"]).to(DEV)
+    coef = torch.ones(4, 2, device=DEV)
+    W, b, lv = t(case["W0"]).to(DEV), t(case["b0"]).to(DEV), torch.full((3,), -7.0, device=DEV)
+    o = _lib.Opt()
+    o.kind, o.lr, o.beta1, o.beta2, o.eps = 0, 0.05, 0.9, 0.999, 1e-8
+    o.one_minus_beta1, o.one_minus_beta2 = 0.1, 0.001
+    p = _lib.ptr
+    good = dict(item_w=p(Q), item_b=p(c), dim=8, num_items=300, hist_ptr=p(ptr), hist_idx=p(idx), neg_idx=p(neg),
+                n_neg=2, n_users=3, loss=2, opt=ctypes.byref(o), step_coef=p(coef), steps=4, user_w=p(W), user_b=p(b),
+                loss_out=p(lv))
+
+    def call(**over):
+        a = dict(good, **over)
+        return lib.rg_mf_fold_in_users(_lib.stream_handle(), *[a[k] for k in good])
+
+    sgd = _lib.Opt()
+    sgd.kind = 1
+    for over, word in ((dict(dim=0), "dim"), (dict(dim=257), "dim"), (dict(n_neg=-1), "n_neg"), (dict(n_neg=33), "n_neg"),
+                       (dict(steps=-1), "steps"), (dict(steps=1025), "steps"), (dict(n_users=-1), "n_users"),
+                       (dict(loss=4), "loss"), (dict(loss=-1), "loss"), (dict(n_neg=0, loss=1), "n_neg"),
+                       (dict(neg_idx=None), "neg_idx"), (dict(opt=ctypes.byref(sgd)), "Adam"),
+                       (dict(num_items=0), "num_items"), (dict(item_w=None), "null"), (dict(user_b=None), "null"),
+                       (dict(hist_ptr=None), "null"), (dict(step_coef=None), "step_coef")):
+        assert call(**over) == -1, over                                  # RG_E_ARG
+        assert word in lib.rg_last_error().decode(), (over, lib.rg_last_error())
+    for over in (dict(steps=0), dict(n_users=0)):                        # RG_OK, nothing written
+        assert call(**over) == 0
+    torch.cuda.synchronize()
+    assert W.cpu().numpy().tobytes() == case["W0"].tobytes() and b.cpu().numpy().tobytes() == case["b0"].tobytes()
+    assert (lv.cpu().numpy() == -7.0).all()
+    assert call() == 0                                                    # and the same arguments in range run
+    torch.cuda.synchronize()
+    assert (W.cpu().numpy()[[0, 2]] != case["W0"][[0, 2]]).any() and W.cpu().numpy()[1].tobytes() == case["W0"][1].tobytes()
+    assert np.isfinite(lv.cpu().numpy()).all() and lv.cpu().numpy()[1] == 0
