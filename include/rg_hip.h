@@ -30,6 +30,9 @@
  *   rg_mf_topk_users    the k best items of those users, scored, excluded and ranked in LDS
  *   rg_mf_fold_in_users rows and biases of NEW users fitted against the frozen item tables
  *                       (the model's loss, Adam; no reference counterpart: it retrains)
+ *   rg_mf_score_lists / a ragged list of candidate items per user scored, and ranked inside
+ *   rg_seg_topk /       each list (re-ranking; the sampled HR / NDCG protocol; no reference
+ *   rg_seg_rank         counterpart: it ranks every item)
  *   rg_topk_rows_wide   the first k <= 1024 entries of argsort(-scores) of a score block
  *                                                          spotlight/evaluation.py:115-213
  *   rg_item_sim_topk    the k rows of an embedding table most similar to each query row
@@ -1008,6 +1011,63 @@ int rg_mf_fold_in_users(void *stream, const float *item_w, const float *item_b, 
                         const int32_t *neg_idx, int32_t n_neg, int64_t n_users, int32_t loss,
                         const rg_opt_t *opt, const float *step_coef, int32_t steps, float *user_w,
                         float *user_b, float *loss_out);
+
+/* ------------------------------------------------------------------------------
+ * Candidate lists (rg_cand.hip): score a ragged list of items per user and rank INSIDE each
+ * list -- re-ranking the candidates of a retrieval stage, and the sampled evaluation protocol
+ * (a held-out item among drawn negatives) -- no reference counterpart (it ranks every item).
+ * The lists are a CSR over the call's n rows (device): list r is list_idx[list_ptr[r] ..
+ * list_ptr[r + 1]), int64 offsets ascending from list_ptr[0], int32 ids, any length from 0 to
+ * 2^31 - 1, repeats allowed.  Each entry is one launch, takes device pointers, allocates
+ * nothing, needs no workspace and uses no atomics.
+ *
+ * rg_mf_score_lists: for every entry e of list r
+ *     out[e] = sigmoid((<user_w[users_dev[r]], item_w[list_idx[e]]> + user_b[users_dev[r]])
+ *                      + item_b[list_idx[e]])
+ * (the bias order of rg_mf_score_users), out [nnz] fp32 in list order, nothing else written.
+ * A list is owned by one group of lanes (the pair kernel's row layout, 64 / lanes lists per
+ * wave, as rg_mf_fold_in_users): the user's row and bias stay in registers while its list is
+ * walked, four gathered item rows in flight per group; a wave loops to its longest list and
+ * masks the shorter ones with selects.  Each score is ONE fixed-order fp32 sum (a lane's
+ * elements ascending, then the group's butterfly) that depends on dim and the tables'
+ * alignment alone: the same (user, item) gives the same bits at any position of any list in
+ * any call.  dim in [1, 256]; 16-byte loads when dim % 4 == 0 and user_w and item_w are
+ * 16-byte aligned, scalar loads otherwise.  The tables are only read; the user ids (int64)
+ * and item ids are trusted to be in range and list_ptr to describe list_idx.
+ *
+ * rg_seg_topk: scores [nnz] (fp32, only read) are the entries' values in list order;
+ *     out_pos[r][0 .. k)   the positions WITHIN list r (0-based) of its first k entries by
+ *                          key descending, then item id ascending, then position ascending --
+ *                          a repeated id appears as often as it is listed.  The key rule is
+ *                          rg_topk_rows_wide's: the key of a NaN is -inf, -0.0 and +0.0 are
+ *                          one key, entries at -inf / NaN come last by the same tie rule;
+ *     out_val[r][j]        the raw value at that position (a NaN stays the NaN it was); may
+ *                          be null.
+ * A list shorter than k fills the rest of its row with position -1 and the value -inf.  Both
+ * device, [n][k], int32 / fp32; 1 <= k <= 32.  The ids are only compared, never used as
+ * indices.  One wave per list walks it 64 entries at a time into a sorted list per lane
+ * (rg_topk_lists.h's order and insertion), then takes the best head of the 64 lists k times.
+ * (key, id, position) is a total order: a list's output depends on that list alone.
+ *
+ * rg_seg_rank: entry 0 of each list is the target; out [n][2] int32 (device):
+ *     out[r][0]   the number of OTHER entries of list r with a strictly higher key,
+ *     out[r][1]   the number of other entries with an equal key and a lower item id
+ * -- together the entries rg_seg_topk places before the target, so the target is among the
+ * first k exactly when out[r][0] + out[r][1] < k.  An empty list writes (-1, -1).
+ *
+ * RG_E_ARG (rg_last_error names the reason, no HIP call made, nothing written) on a null
+ * pointer (out_val alone may be null), dim outside [1, 256], k outside [1, 32], n < 0, or more
+ * lists than one launch takes (2^31 - 1 workgroups); n == 0: RG_OK, no launch.  (The entries
+ * cannot see the lists' lengths: a caller with no entries at all has nothing to pass for
+ * scores / list_idx and fills its outputs itself, as candidates.py does.)
+ * ---------------------------------------------------------------------------- */
+int rg_mf_score_lists(void *stream, const float *user_w, const float *item_w, const float *user_b,
+                      const float *item_b, int32_t dim, const int64_t *users_dev, const int64_t *list_ptr,
+                      const int32_t *list_idx, int64_t n, float *out);
+int rg_seg_topk(void *stream, const float *scores, const int64_t *list_ptr, const int32_t *list_idx,
+                int64_t n, int32_t k, int32_t *out_pos, float *out_val);
+int rg_seg_rank(void *stream, const float *scores, const int64_t *list_ptr, const int32_t *list_idx,
+                int64_t n, int32_t *out);
 
 /* ------------------------------------------------------------------------------
  * Item-to-item similarity (rg_item_sim.hip): the k rows of an embedding table most similar

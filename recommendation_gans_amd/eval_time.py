@@ -120,6 +120,15 @@ loss; ids on the device going in, rows on the device coming out.  Device events,
 path, the peak device memory of one call of each, the largest difference of the two results, and
 the kernel's time against max(gathered bytes at 8 TB/s, flops at the fp32 vector peak).  One JSON
 line per shape.
+
+    python -m recommendation_gans_amd.eval_time --metric candidates [--items 26744] [--reps 20]
+
+times candidate-list scoring and ranking, 100 candidates per user and k = 10 at 256 and 4096 users:
+MF (d in {32, 64, 128}) through ``candidates.score_lists`` + ``seg_topk`` against the torch chain and
+against the full score block + gather + rg_topk_rows, NCF (E = 64) through ``NCFEngine.scores`` +
+``seg_topk`` against ``NCFEngine.scores_torch`` + ``torch.topk``; the paths alternate in one process,
+device events, min / median and the peak device memory of one call of each.  One JSON line per model
+and shape.
 """
 import argparse
 import contextlib
@@ -648,6 +657,113 @@ def main_fold_in(args):
     return out
 
 
+def _peak_mb(fn, dev):
+    """Peak device memory of one call of fn above what was allocated before it, in MB."""
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    base = torch.cuda.memory_allocated(dev)
+    torch.cuda.reset_peak_memory_stats(dev)
+    out = fn()
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated(dev) - base
+    del out
+    return peak / 1e6
+
+
+def main_candidates(args):
+    """``--metric candidates``: score and rank 100 candidates per user out of ``--items`` items, k = 10,
+    for 256 and 4096 users: MF at d in {32, 64, 128} -- ``candidates.score_lists`` + ``seg_topk``
+    (rg_mf_score_lists, rg_seg_topk) against (a) the torch chain (``score_lists_torch``, ``torch.topk``
+    on the (users, 100) view) and (b) what existed before: the full score block
+    (``mf_engine.score_users_block``), ``gather`` of the candidates' columns, rg_topk_rows on the
+    gathered block -- and NCF at E = 64: ``NCFEngine.scores`` (users repeated per entry) + ``seg_topk``
+    against ``NCFEngine.scores_torch`` + ``torch.topk``.  Ids and lists are on the device going in
+    (checked once, here), positions on the device coming out; the paths alternate in one process,
+    median of ``--reps`` device-event measurements, and the peak device memory of one call of each.
+    One JSON line per model and shape (profiles/candidates/eval_time_candidates.jsonl holds a run)."""
+    from . import _lib, candidates as cand, mf_engine
+    dev = torch.device("cuda:0")
+    U, I, C, k = 138493, args.items, 100, 10
+    lib = _lib.load()
+    out = []
+
+    def lists(n):
+        rs = np.random.RandomState(n)
+        users = torch.from_numpy(rs.randint(0, U, n)).to(dev)
+        idx = torch.from_numpy(rs.randint(0, I, (n, C)).astype(np.int32)).to(dev)
+        ptr = torch.arange(n + 1, dtype=torch.int64, device=dev) * C
+        return users, ptr, idx
+
+    def measure(paths):
+        for _ in range(3):                                   # warm-up: code objects, allocator
+            for fn in paths.values():
+                fn()
+        torch.cuda.synchronize()
+        ts = {name: [] for name in paths}
+        for _ in range(args.reps):                           # alternate the paths
+            for name, fn in paths.items():
+                ts[name] += timed(fn, 1)
+        return ({name + "_ms": stats(t) for name, t in ts.items()},
+                {name + "_peak_mb": _peak_mb(fn, dev) for name, fn in paths.items()})
+
+    def emit(r):
+        print(json.dumps(r), flush=True)
+        out.append(r)
+
+    for d in (32, 64, 128):
+        g = torch.Generator().manual_seed(d)
+        tabs = [(torch.randn(U, d, generator=g) / d ** 0.5).to(dev), (torch.randn(I, d, generator=g) / d ** 0.5).to(dev),
+                (0.1 * torch.randn(U, generator=g)).to(dev), (0.1 * torch.randn(I, generator=g)).to(dev)]
+        for n in (256, 4096):
+            users, ptr, idx = lists(n)
+            idx64 = idx.to(torch.int64)
+
+            def kernel():
+                return cand.seg_topk(cand.score_lists(*tabs, users, ptr, idx.reshape(-1), checked=True), ptr,
+                                     idx.reshape(-1), k, checked=True)
+
+            def torch_chain():
+                s = cand.score_lists_torch(*tabs, users, ptr, idx.reshape(-1))
+                return torch.topk(s.view(n, C), k, dim=1).indices
+
+            def block():
+                blk = mf_engine.score_users_block(*tabs, users, checked=True)
+                sub = torch.gather(blk, 1, idx64)
+                pos = torch.empty(n, k, dtype=torch.int32, device=dev)
+                _lib.check(lib.rg_topk_rows(_lib.stream_handle(), _lib.ptr(sub), n, C, C, k, _lib.ptr(pos)),
+                           "rg_topk_rows")
+                return pos
+            ms, mb = measure({"kernel": kernel, "torch": torch_chain, "block": block})
+            a = cand.score_lists(*tabs, users, ptr, idx.reshape(-1))
+            b = cand.score_lists_torch(*tabs, users, ptr, idx.reshape(-1))
+            r = {"metric": "candidates", "model": "mf", "dim": d, "users": n, "items": I, "candidates": C, "k": k,
+                 "reps": args.reps, **ms, **mb, "max_abs_diff": float((a - b).abs().max()),
+                 "speedup_vs_torch_median": ms["torch_ms"]["median"] / ms["kernel_ms"]["median"],
+                 "speedup_vs_block_median": ms["block_ms"]["median"] / ms["kernel_ms"]["median"]}
+            emit(r)
+        del tabs
+        torch.cuda.empty_cache()
+    E = 64
+    eng = make_engine(E, 0, U, I, dev)
+    for n in (256, 4096):
+        users, ptr, idx = lists(n)
+        rep, idx64 = torch.repeat_interleave(users, C), idx.reshape(-1).to(torch.int64)
+
+        def kernel():
+            return cand.seg_topk(eng.scores(torch.repeat_interleave(users, ptr[1:] - ptr[:-1]), idx64), ptr,
+                                 idx.reshape(-1), k, checked=True)
+
+        def torch_chain():
+            return torch.topk(eng.scores_torch(torch.repeat_interleave(users, C), idx64).view(n, C), k, dim=1).indices
+        ms, mb = measure({"kernel": kernel, "torch": torch_chain})
+        r = {"metric": "candidates", "model": "ncf", "dim": E, "users": n, "items": I, "candidates": C, "k": k,
+             "reps": args.reps, **ms, **mb,
+             "max_abs_diff": float((eng.scores(rep, idx64) - eng.scores_torch(rep, idx64)).abs().max()),
+             "speedup_vs_torch_median": ms["torch_ms"]["median"] / ms["kernel_ms"]["median"]}
+        emit(r)
+    return out
+
+
 def main_topk_wide(args):
     """``--metric topk_wide``: rg_topk_rows_wide on one score block already on the device, against
     the host path it replaces in the @k metrics above k = 32 (the block to the host, argsort per row)
@@ -908,7 +1024,8 @@ def main_scores(args):
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--metric", choices=("scores", "mrr", "slates", "pairs", "mf_scores", "mf_topk", "item_sim",
-                                        "gan_recommend", "topk_wide", "gan_score", "fold_in"), default="scores")
+                                        "gan_recommend", "topk_wide", "gan_score", "fold_in", "candidates"),
+                    default="scores")
     ap.add_argument("--batch", type=int, default=8192)
     ap.add_argument("--users", type=int, default=None)
     ap.add_argument("--hist-len", type=int, default=128)
@@ -925,7 +1042,7 @@ def main(argv=None):
     return {"scores": main_scores, "mrr": main_mrr, "slates": main_slates, "pairs": main_pairs,
             "mf_scores": main_mf_scores, "mf_topk": main_mf_topk, "item_sim": main_item_sim,
             "gan_recommend": main_gan_recommend, "topk_wide": main_topk_wide,
-            "gan_score": main_gan_score, "fold_in": main_fold_in}[args.metric](args)
+            "gan_score": main_gan_score, "fold_in": main_fold_in, "candidates": main_candidates}[args.metric](args)
 
 
 if __name__ == "__main__":

@@ -135,6 +135,37 @@ def _histories_csr(histories, num_items):
     return ptr, idx.astype(np.int32)
 
 
+def _candidate_lists(candidates, n, num_items):
+    """Candidate lists as a CSR over item ids, (indptr int64 [n + 1], indices int32): a scipy sparse
+    matrix with ``num_items`` columns (its rows, indices as stored), an ``(n, C)`` integer array, or a
+    list of id sequences (each in the order given, repeats kept).  ValueError for another number of
+    lists than ``n`` users, another width, ids that are not integers or an id outside [0, num_items)."""
+    if hasattr(candidates, "tocsr"):
+        csr = candidates.tocsr()
+        if csr.shape[1] != num_items:
+            raise ValueError(f"candidates have {csr.shape[1]} columns, the model {num_items} items")
+        rows, ptr, idx = csr.shape[0], csr.indptr.astype(np.int64), csr.indices.astype(np.int64)
+    elif isinstance(candidates, np.ndarray) and candidates.ndim == 2:
+        if candidates.dtype.kind not in "iu":
+            raise ValueError("candidates must hold integer item ids")
+        rows = candidates.shape[0]
+        ptr = np.arange(rows + 1, dtype=np.int64) * candidates.shape[1]
+        idx = candidates.astype(np.int64).reshape(-1)
+    else:
+        lists = [np.asarray(r).reshape(-1) for r in candidates]
+        if any(len(r) and r.dtype.kind not in "iu" for r in lists):
+            raise ValueError("candidates must hold integer item ids")
+        rows = len(lists)
+        ptr = np.zeros(rows + 1, dtype=np.int64)
+        np.cumsum([len(r) for r in lists], out=ptr[1:])
+        idx = np.concatenate(lists).astype(np.int64) if ptr[-1] else np.zeros(0, dtype=np.int64)
+    if rows != n:
+        raise ValueError(f"{rows} candidate lists for {n} users")
+    if len(idx) and (idx.min() < 0 or idx.max() >= num_items):
+        raise ValueError("candidate item id outside [0, num_items)")
+    return ptr, idx.astype(np.int32)
+
+
 def _fold_negatives(nnz, n_neg, num_items, random_state, device=None):
     """The fold-in's negatives, drawn once: ``random_state.randint(0, num_items, nnz * n_neg)`` --
     uniform over the items, so one may coincide with a positive, as in the reference -- through the
@@ -549,6 +580,90 @@ class ImplicitFactorizationModel:
             if return_scores:
                 scores[s:s + len(ub)] = torch.gather(blk, 1, out.to(torch.int64)).cpu().numpy()
         return (ids, scores) if return_scores else ids
+
+    def _candidate_blocks(self, user_ids, candidates, what):
+        """The checks ``score_candidates`` and ``rank_candidates`` share, then per block of 4096 users
+        (first user, last, ptr and idx on the device with ptr starting at 0, the entries' scores on the
+        device).  MF scores through ``candidates.score_lists`` on ``_tables()`` (the gathered full
+        tables after a data-parallel fit), NCF / NeuMF through ``NCFEngine.scores`` -- the pair kernel
+        behind ``predict`` -- with the users repeated per entry on the device."""
+        from . import candidates as cand
+        if not self._initialized:
+            raise RuntimeError(f"{what} needs a fitted model")
+        users = np.asarray(user_ids, dtype=np.int64).reshape(-1)
+        n = len(users)
+        if n and (users.min() < 0 or users.max() >= self._num_users):
+            raise ValueError("user id outside [0, num_users)")
+        ptr, idx = _candidate_lists(candidates, n, self._num_items)
+        dev = self._engine.device
+
+        def blocks():
+            for s in range(0, n, 4096):
+                e = min(s + 4096, n)
+                p = torch.as_tensor(ptr[s:e + 1] - ptr[s], device=dev)
+                i = torch.as_tensor(idx[ptr[s]:ptr[e]], device=dev)
+                u = torch.as_tensor(users[s:e], device=dev)
+                if self._kind == "mf":
+                    U, I, ub, ib = self._tables()
+                    sc = cand.score_lists(U.contiguous(), I.contiguous(), ub.reshape(-1).contiguous(),
+                                          ib.reshape(-1).contiguous(), u, p, i, checked=True)
+                else:
+                    sc = self._engine.scores(torch.repeat_interleave(u, p[1:] - p[:-1]), i.to(torch.int64))
+                yield s, e, p, i, sc
+        return n, ptr, blocks()
+
+    def score_candidates(self, user_ids, candidates):
+        """The scores of a list of candidate items per user: a flat float32 host array in list order
+        (user 0's candidates first).  ``candidates``: a list of item-id sequences (one per user, any
+        lengths, repeats allowed), an ``(n, C)`` integer array, or a scipy sparse matrix with
+        ``num_items`` columns (its rows' indices as stored).  Only the lists go up and the scores come
+        down, 4096 users at a time: MF through rg_mf_score_lists (``candidates.score_lists``: no
+        (users, items) block), NCF / NeuMF through the pair kernel behind ``predict``, whose bits
+        these are.  ValueError for an id outside the model or a number of lists other than
+        ``len(user_ids)``."""
+        n, ptr, blocks = self._candidate_blocks(user_ids, candidates, "score_candidates")
+        out = np.empty(int(ptr[-1]), dtype=np.float32)
+        for s, e, _, _, sc in blocks:
+            out[ptr[s]:ptr[e]] = sc.cpu().numpy()
+        return out
+
+    def rank_candidates(self, user_ids, candidates, k=10, return_scores=False):
+        """The k best of each user's candidate items (re-ranking): ``(len(user_ids), k)`` int64 item ids
+        on the host in rank order -- higher score first, then the lower item id; an id listed twice
+        may be returned twice -- with -1 where a list has fewer than k entries, and with
+        ``return_scores`` also their float32 scores (-inf there).  ``candidates`` as in
+        ``score_candidates``, whose scores these rank: scored on the device, then rg_seg_topk
+        (``candidates.seg_topk``) inside each list; only ids and scores come down.  ValueError for an
+        id outside the model, k outside [1, 32] or a number of lists other than ``len(user_ids)``."""
+        from . import candidates as cand
+        if int(k) != k or k < 1 or k > cand.SEG_TOPK_MAX:
+            raise ValueError(f"k must be in [1, {cand.SEG_TOPK_MAX}]")
+        k = int(k)
+        n, ptr, blocks = self._candidate_blocks(user_ids, candidates, "rank_candidates")
+        ids = np.full((n, k), -1, dtype=np.int64)
+        scores = np.full((n, k), -np.inf, dtype=np.float32)
+        for s, e, p, i, sc in blocks:
+            if not i.numel():
+                continue
+            pos, val = cand.seg_topk(sc, p, i, k, return_values=True, checked=True)
+            at = (p[:-1, None] + pos.clamp(min=0)).clamp(max=i.numel() - 1)
+            ids[s:e] = torch.where(pos >= 0, i[at].to(torch.int64), -1).cpu().numpy()
+            if return_scores:
+                scores[s:e] = val.cpu().numpy()
+        return (ids, scores) if return_scores else ids
+
+    def candidate_target_ranks(self, user_ids, candidates):
+        """Where the FIRST entry of each user's candidate list (the target) stands among the rest, as
+        ``evaluation.sampled_hit_ndcg`` reads it: ``(len(user_ids), 2)`` int64 on the host, the other
+        entries with a higher score and those with an equal score and a lower item id, (-1, -1) for
+        an empty list.  Scored like ``score_candidates``, counted on the device (rg_seg_rank,
+        ``candidates.seg_rank``); two counts per list come down."""
+        from . import candidates as cand
+        n, ptr, blocks = self._candidate_blocks(user_ids, candidates, "candidate_target_ranks")
+        out = np.full((n, 2), -1, dtype=np.int64)
+        for s, e, p, i, sc in blocks:
+            out[s:e] = cand.seg_rank(sc, p, i, checked=True).cpu().numpy()
+        return out
 
     def _fold_in_device(self, histories, steps, lr, n_neg, l2, random_state, return_loss):
         """``fold_in_users`` up to the device results: (indptr, indices, (W, b[, loss]) on the device)."""

@@ -201,6 +201,148 @@ def map_at_k(model, test, k=5):
     return np.mean(np.array(vals).squeeze())
 
 
+class _PredictRows:
+    """``score_users`` over a model that has only the reference's ``predict(user)``."""
+
+    def __init__(self, model):
+        self._model = model
+
+    def score_users(self, users):
+        return np.stack([np.asarray(self._model.predict(int(u)), dtype=np.float32) for u in users])
+
+
+def ndcg_at_k(model, test, train=None, k=10):
+    """Mean binary-relevance NDCG@k over the FULL ranking (no reference counterpart): per test user
+    with items, DCG = sum over the ranks j < k that hold one of its test items of 1 / log2(j + 2),
+    IDCG the same sum over the first min(n_test, k) ranks; train items rank last.  float64 on the
+    host, from the device top-k's hits (``_topk_hits``) where ``_device_topk(model, k)`` holds, from
+    ``_ranked`` otherwise."""
+    test_csr = test.tocsr()
+    train_csr = train.tocsr() if train is not None else None
+    k = int(k)
+    disc = 1.0 / np.log2(np.arange(k, dtype=np.float64) + 2.0)
+    ideal = np.cumsum(disc)
+    if _device_topk(model, k):
+        _, hits, n_t = _topk_hits(model, test_csr, train_csr, k)
+    else:
+        if not hasattr(model, "score_users"):       # a model with ``predict`` alone: one call per user
+            model = _PredictRows(model)
+        rows = [(np.isin(np.asarray(ranking[:k]), targets), len(targets))
+                for _, targets, ranking in _ranked(model, test_csr, train_csr, k=k)]
+        hits = np.array([np.pad(h, (0, k - len(h))) for h, _ in rows], dtype=bool).reshape(len(rows), k)
+        n_t = np.array([n for _, n in rows], dtype=np.int64)
+    dcg = np.zeros(len(n_t), dtype=np.float64)
+    for j in range(k):                      # one rank at a time: the same sum on either path
+        dcg = np.where(hits[:, j], dcg + disc[j], dcg)
+    return np.mean(dcg / ideal[np.minimum(n_t, k) - 1])
+
+
+def _interaction_keys(csr):
+    rows = np.repeat(np.arange(csr.shape[0], dtype=np.int64), np.diff(csr.indptr))
+    return rows * np.int64(csr.shape[1]) + csr.indices.astype(np.int64)
+
+
+def sampled_candidate_lists(test, train=None, n_negatives=99, random_state=None):
+    """The candidate lists of the sampled evaluation protocol (He et al., Neural Collaborative
+    Filtering, 2017): one list per test interaction (the distinct (user, item) entries of
+    ``test.tocsr()``, in its order), ``[target, negatives...]`` with ``n_negatives`` distinct items
+    drawn uniformly from those in neither the user's test row nor its train row.  Returns ``(users
+    int64 [m], ptr int64 [m + 1], idx int32 [m (1 + n_negatives)])``, the CSR ``score_candidates``
+    and ``candidates.seg_rank`` take.  The draw is vectorised on the host -- draw every list at once,
+    look the draws up in the sorted ``user * num_items + item`` keys of test and train, redraw only
+    the collisions (and repeats within a list) -- from ``random_state`` (default
+    ``np.random.RandomState(0)``): an equal seed reproduces it.  ValueError if some test user has
+    fewer than ``n_negatives`` eligible items."""
+    test_csr = test.tocsr()
+    n_neg = int(n_negatives)
+    if n_neg < 0:
+        raise ValueError("n_negatives must be >= 0")
+    rs = random_state if random_state is not None else np.random.RandomState(0)
+    I = np.int64(test_csr.shape[1])
+    keys = _interaction_keys(test_csr)
+    if train is not None:
+        train_csr = train.tocsr()
+        if train_csr.shape != test_csr.shape:
+            raise ValueError(f"train has shape {train_csr.shape}, test {test_csr.shape}")
+        keys = np.concatenate([keys, _interaction_keys(train_csr)])
+    keys = np.unique(keys)
+    users = np.repeat(np.arange(test_csr.shape[0], dtype=np.int64), np.diff(test_csr.indptr))
+    targets = test_csr.indices.astype(np.int64)
+    m = len(users)
+    taken = np.bincount(keys // I, minlength=test_csr.shape[0])
+    if m and n_neg and (I - taken[users]).min() < n_neg:
+        raise ValueError(f"a test user has fewer than {n_neg} items outside its test and train rows")
+    neg = rs.randint(0, I, size=(m, n_neg)).astype(np.int64)
+
+    def clashes(block, block_users):
+        q = block_users[:, None] * I + block
+        at = np.minimum(np.searchsorted(keys, q), max(len(keys) - 1, 0))
+        bad = keys[at] == q if len(keys) else np.zeros(q.shape, bool)
+        order = np.argsort(block, axis=1, kind="stable")         # a repeat: the later position is redrawn
+        srt = np.take_along_axis(block, order, axis=1)
+        rep = np.zeros(block.shape, bool)
+        rep[:, 1:] = srt[:, 1:] == srt[:, :-1]
+        dup = np.zeros(block.shape, bool)
+        np.put_along_axis(dup, order, rep, axis=1)
+        return bad | dup
+
+    if m and n_neg:
+        live = np.arange(m)
+        for _ in range(64):
+            bad = clashes(neg[live], users[live])
+            hit = bad.any(axis=1)
+            live, bad = live[hit], bad[hit]
+            if not len(live):
+                break
+            sub = neg[live]
+            sub[bad] = rs.randint(0, I, size=int(bad.sum()))
+            neg[live] = sub
+        else:
+            # lists still clashing (a user with hardly more eligible items than n_negatives): drawn exactly
+            for r in live:
+                u = users[r]
+                lo, hi = np.searchsorted(keys, [u * I, (u + 1) * I])
+                free = np.setdiff1d(np.arange(I, dtype=np.int64), keys[lo:hi] - u * I, assume_unique=True)
+                neg[r] = rs.choice(free, n_neg, replace=False)
+    idx = np.concatenate([targets[:, None], neg], axis=1).astype(np.int32).reshape(-1)
+    return users, np.arange(m + 1, dtype=np.int64) * (1 + n_neg), idx
+
+
+def _ahead_host(scores, idx, width):
+    """seg_rank's counts on the host for lists of one width: (m, 2) int64, the entries with a higher
+    key than entry 0 and those with an equal key and a lower item id (the key of a NaN is -inf)."""
+    s = np.asarray(scores, dtype=np.float32).reshape(-1, width)
+    s = np.where(np.isnan(s), np.float32(-np.inf), s)
+    i = np.asarray(idx).reshape(-1, width)
+    above = (s[:, 1:] > s[:, :1]).sum(axis=1)
+    tied = ((s[:, 1:] == s[:, :1]) & (i[:, 1:] < i[:, :1])).sum(axis=1)
+    return np.stack([above, tied], axis=1).astype(np.int64)
+
+
+def sampled_hit_ndcg(model, test, train=None, n_negatives=99, k=10, random_state=None):
+    """(HR@k, NDCG@k) of the sampled protocol the NCF paper reports (its 99 negatives and k = 10 are
+    the defaults): every test interaction is ranked among the ``n_negatives`` items of its list
+    (``sampled_candidate_lists``), ahead = the candidates with a higher score plus those with an equal
+    score and a lower item id, HR = mean(ahead < k), NDCG = mean(1 / log2(ahead + 2) where ahead < k,
+    else 0).  A model with ``score_candidates`` scores and counts on the device
+    (``candidate_target_ranks`` -> rg_seg_rank: two counts per interaction come down); any other
+    model takes the host path over ``model.predict(users, items)`` with the same ordering rule."""
+    users, ptr, idx = sampled_candidate_lists(test, train, n_negatives, random_state)
+    if not len(users):
+        raise ValueError("sampled_hit_ndcg: the test set has no interactions")
+    width = 1 + int(n_negatives)
+    if hasattr(model, "score_candidates") and hasattr(model, "candidate_target_ranks"):
+        counts = np.asarray(model.candidate_target_ranks(users, idx.reshape(-1, width)), dtype=np.int64)
+    elif hasattr(model, "score_candidates"):
+        counts = _ahead_host(model.score_candidates(users, idx.reshape(-1, width)), idx, width)
+    else:
+        counts = _ahead_host(model.predict(np.repeat(users, width), idx.astype(np.int64)), idx, width)
+    ahead = counts.sum(axis=1)
+    hit = ahead < int(k)
+    gain = np.where(hit, 1.0 / np.log2(ahead.astype(np.float64) + 2.0), 0.0)
+    return float(np.mean(hit)), float(np.mean(gain))
+
+
 def evaluate_popItems(item_popularity, test, k=10):
     test = test.tocsr()
     pop = np.asarray(getattr(item_popularity, "values", item_popularity))

@@ -1,0 +1,244 @@
+"""What the candidate-list tests share (no tests here): the ragged cases for rg_seg_topk / rg_seg_rank
+with their numpy references, the MF tables and the error bound of rg_mf_score_lists, the float64
+reference behind the model-level comparison with ``recommend``, and the stub models of the CPU tests."""
+import numpy as np
+import torch
+
+LENGTHS = [0, 1, 2, 31, 32, 33, 63, 64, 65, 200, 1000]
+KS = [1, 10, 32]
+SEG_KINDS = ["random", "repeats", "quantised", "special"]
+NUM_ITEMS = 300
+EPS = 2.0 ** -24
+
+
+def list_ptr(lengths):
+    return np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+
+
+def seg_case(kind, seed=0):
+    """(scores float32 [nnz], ptr int64, idx int32): every length of LENGTHS twice, in a shuffled
+    order.  "random": distinct ids per list where the catalogue allows, continuous scores; "repeats":
+    ids from 7 values, so most entries share an id; "quantised": scores on 8 levels, ties are the rule
+    (ids repeat too); "special": NaN, +-inf and +-0.0 among quantised scores."""
+    rs = np.random.RandomState(seed)
+    lengths = rs.permutation(np.array(LENGTHS + LENGTHS))
+    ptr = list_ptr(lengths)
+    nnz = int(ptr[-1])
+    if kind == "random":
+        idx = np.concatenate([rs.permutation(max(n, NUM_ITEMS))[:n] for n in lengths])
+        scores = rs.rand(nnz)
+    elif kind == "repeats":
+        idx = rs.randint(0, 7, nnz)
+        scores = rs.rand(nnz)
+    elif kind == "quantised":
+        idx = rs.randint(0, NUM_ITEMS, nnz)
+        scores = rs.randint(0, 8, nnz) / 8.0
+    else:
+        idx = rs.randint(0, 40, nnz)
+        scores = rs.randint(-2, 3, nnz) / 4.0
+        special = np.array([np.nan, np.inf, -np.inf, 0.0, -0.0, -np.nan])
+        at = rs.rand(nnz) < 0.5
+        scores[at] = special[rs.randint(0, len(special), int(at.sum()))]
+    return scores.astype(np.float32), ptr, idx.astype(np.int32)
+
+
+def keys(scores):
+    """The key rule: the key of a NaN is -inf, -0.0 and +0.0 are one key."""
+    s = np.asarray(scores, dtype=np.float32)
+    return np.where(np.isnan(s), np.float32(-np.inf), s) + np.float32(0.0)
+
+
+def ref_topk(scores, ptr, idx, k):
+    """Positions within each list by np.lexsort on (position, item id, -key); -1 past the list's end."""
+    out = np.full((len(ptr) - 1, k), -1, dtype=np.int32)
+    key = keys(scores)
+    for r in range(len(ptr) - 1):
+        lo, hi = ptr[r], ptr[r + 1]
+        order = np.lexsort((np.arange(hi - lo), idx[lo:hi], -key[lo:hi]))[:k]
+        out[r, :len(order)] = order
+    return out
+
+
+def ref_rank(scores, ptr, idx):
+    out = np.full((len(ptr) - 1, 2), -1, dtype=np.int32)
+    key = keys(scores)
+    for r in range(len(ptr) - 1):
+        lo, hi = ptr[r], ptr[r + 1]
+        if hi > lo:
+            out[r, 0] = (key[lo + 1:hi] > key[lo]).sum()
+            out[r, 1] = ((key[lo + 1:hi] == key[lo]) & (idx[lo + 1:hi] < idx[lo])).sum()
+    return out
+
+
+def take_lists(scores, ptr, idx, rows):
+    """The lists ``rows`` (in that order) as a call of their own."""
+    rows = np.asarray(rows)
+    take = np.concatenate([np.arange(ptr[r], ptr[r + 1]) for r in rows] + [np.zeros(0, np.int64)]).astype(np.int64)
+    return scores[take], list_ptr(np.diff(ptr)[rows]), idx[take]
+
+
+# ---------------------------------------------------------------- rg_mf_score_lists
+SCORE_DIMS = [1, 3, 16, 64, 65, 256]
+SCORE_USERS = [1, 5, 130]
+
+
+def mf_tables(dim, num_users=50, num_items=NUM_ITEMS, seed=0):
+    rs = np.random.RandomState(seed)
+    f = np.float32
+    return ((rs.randn(num_users, dim) / np.sqrt(dim)).astype(f), (rs.randn(num_items, dim) * 2).astype(f),
+            rs.randn(num_users).astype(f), rs.randn(num_items).astype(f))
+
+
+def score_case(n_lists, num_users=50, num_items=NUM_ITEMS, seed=0):
+    """(users int64 [n], ptr, idx): users drawn with repeats, the lengths of LENGTHS cycled through the
+    lists in a shuffled order, ids with repeats."""
+    rs = np.random.RandomState(seed)
+    users = rs.randint(0, num_users, n_lists).astype(np.int64)
+    lengths = np.resize(rs.permutation(LENGTHS), n_lists)
+    ptr = list_ptr(lengths)
+    return users, ptr, rs.randint(0, num_items, int(ptr[-1])).astype(np.int32)
+
+
+def mf_reference(tables, users, ptr, idx):
+    """(float64 scores by ``score_lists_torch`` on float64 CPU copies, the bound per score)."""
+    from recommendation_gans_amd.candidates import score_lists_torch
+    U, I, ub, ib = (torch.from_numpy(np.asarray(t, dtype=np.float64)) for t in tables)
+    t = torch.from_numpy
+    ref = score_lists_torch(U, I, ub, ib, t(users), t(ptr), t(idx)).numpy()
+    rows = np.repeat(np.arange(len(users)), np.diff(ptr))
+    u, i = users[rows], idx.astype(np.int64)
+    return ref, mf_bound(U.numpy()[u], I.numpy()[i], ub.numpy()[u], ib.numpy()[i])
+
+
+def mf_bound(p, q, b, c):
+    """0.25 (dim + 2) 2^-24 (sum_k |p_k q_k| + |b| + |c|) + 4 2^-24 per row of float64 (p, q, b, c): a
+    first-order bound on a length-(dim + 2) fp32 sum through the sigmoid's slope (<= 1/4), plus expf
+    and the division."""
+    dim = p.shape[-1]
+    return 0.25 * (dim + 2) * EPS * (np.abs(p * q).sum(-1) + np.abs(b) + np.abs(c)) + 4 * EPS
+
+
+# ---------------------------------------------------------------- model level
+MODEL_U, MODEL_I, MODEL_E, MODEL_M, MODEL_K = 40, NUM_ITEMS, 16, 5, 10
+NCF_RTOL, NCF_ATOL = 1e-5, 1e-7     # the project's tolerance of the NCF / NeuMF kernels against float64
+
+
+def model_block64(kind):
+    """The float64 (users, items) score block of ``make_model(kind, ..., MODEL_U, MODEL_I, ...)``'s
+    network -- built here on the CPU by the same calls from the same seed, so no GPU is needed -- and
+    the error allowed per score: the MF bound above, or the NCF / NeuMF kernels' tolerance."""
+    from oracle.ncf import layer_sizes
+    from recommendation_gans_amd.spotlight.dnn_models.mlp import MLP
+    from recommendation_gans_amd.spotlight.dnn_models.neuMF import NeuMF
+    from recommendation_gans_amd.spotlight.factorization.representations import BilinearNet
+    from tests.ncf_infer_common import forward64
+    U, I, E, M = MODEL_U, MODEL_I, MODEL_E, MODEL_M
+    torch.manual_seed(11)
+    if kind == "mf":
+        # make_model's own N(0, 1) tables put the best scores of a row within float32's spacing below
+        # 1.0; the GPU test loads these tables into the model instead (``load_tables``)
+        p, q, b, c = (np.asarray(t, dtype=np.float64) for t in untied_tables())
+        z = p @ q.T + b.reshape(-1, 1) + c.reshape(1, -1)
+        bound = mf_bound(p[:, None, :], q[None, :, :], b.reshape(-1, 1), c.reshape(1, -1))
+        return 1.0 / (1.0 + np.exp(-z)), bound
+    if kind == "ncf":
+        net = MLP(layers=layer_sizes(E), num_users=U, num_items=I, embedding_dim=E)
+    else:
+        net = NeuMF(layer_sizes(E), U, I, mf_embedding_dim=M, mlp_embedding_dim=E)
+    params = [w.detach().numpy() for _, w in net.named_parameters()]
+    blk = forward64(params, M if kind == "neumf" else 0)
+    return blk, NCF_RTOL * np.abs(blk) + NCF_ATOL
+
+
+def separated_rows(kind, k=MODEL_K):
+    """Rows of the float64 block whose first k + 1 scores (rank order) are pairwise further apart than
+    twice the allowed error: there a float32 ranking of the first k cannot differ from the float64 one."""
+    blk, bound = model_block64(kind)
+    order = np.argsort(-blk, axis=1, kind="stable")[:, :k + 1]
+    top = np.take_along_axis(blk, order, axis=1)
+    tol = np.take_along_axis(np.broadcast_to(bound, blk.shape), order, axis=1)
+    gap = top[:, :-1] - top[:, 1:]                  # sorted: neighbours are the closest pairs
+    return (gap > 2 * np.maximum(tol[:, :-1], tol[:, 1:])).all(axis=1)
+
+
+# ---------------------------------------------------------------- the sampled protocol
+SAMPLED_N_TEST, SAMPLED_NEG, SAMPLED_SEED = 120, 99, 5
+
+
+def model_interactions(n_test=SAMPLED_N_TEST, U=MODEL_U, I=MODEL_I):
+    """(train, test) as scipy matrices: ``make_model``'s own draws (same generator, same order)."""
+    import scipy.sparse as sp
+    rs = np.random.RandomState(4)
+    tr = (rs.randint(0, U, 600), rs.randint(0, I, 600))
+    te = (rs.randint(0, U, n_test), rs.randint(0, I, n_test))
+    one = np.ones
+    return (sp.coo_matrix((one(600, np.float32), tr), shape=(U, I)),
+            sp.coo_matrix((one(n_test, np.float32), te), shape=(U, I)))
+
+
+def untied_tables():
+    """MF tables of the model's shape for the sampled protocol's comparison of the two paths."""
+    return mf_tables(MODEL_E, MODEL_U, MODEL_I, seed=SAMPLED_SEED)
+
+
+def load_tables(model, tables):
+    """Overwrite an MF model's tables (engine and network) with host arrays."""
+    ts = [torch.from_numpy(np.ascontiguousarray(t)) for t in tables]
+    model._engine.set_params(*ts)
+    model._load_into_net(ts)
+
+
+def quantised_tables(seed=3):
+    """MF tables on a grid of 1/4: every product and sum is exact in float32 in any order, so equal
+    scores in float64 are equal in float32 on every path, and ties are frequent."""
+    rs = np.random.RandomState(seed)
+    f = np.float32
+    return (rs.randint(-2, 3, (MODEL_U, MODEL_E)).astype(f) / 4, rs.randint(-2, 3, (MODEL_I, MODEL_E)).astype(f) / 4,
+            rs.randint(-2, 3, MODEL_U).astype(f) / 4, rs.randint(-2, 3, MODEL_I).astype(f) / 4)
+
+
+def target_margins(tables, users, ptr, idx):
+    """Per list of the sampled protocol: the smallest |score(target) - score(other)| in float64 less
+    twice the larger of the two entries' bounds.  Positive: no float32 evaluation within the bound can
+    order the target and that entry differently."""
+    ref, bound = mf_reference(tables, users, ptr, idx)
+    w = int(ptr[1] - ptr[0])
+    s, b = ref.reshape(-1, w), bound.reshape(-1, w)
+    return (np.abs(s[:, 1:] - s[:, :1]) - 2 * np.maximum(b[:, 1:], b[:, :1])).min(axis=1)
+
+
+# ---------------------------------------------------------------- stub models (CPU tests)
+class PredictOnly:
+    """A model over a fixed (users, items) score table that exposes only ``predict``."""
+
+    def __init__(self, scores):
+        self.s = np.asarray(scores, dtype=np.float32)
+
+    def predict(self, user_ids, item_ids=None):
+        if item_ids is None:
+            return self.s[int(user_ids)].copy()
+        return self.s[np.asarray(user_ids), np.asarray(item_ids)]
+
+
+class ScoreUsersOnly:
+    """The same table behind ``score_users`` (the metrics' host path)."""
+
+    def __init__(self, scores):
+        self.s = np.asarray(scores, dtype=np.float32)
+
+    def score_users(self, users):
+        return self.s[np.asarray(users)].copy()
+
+
+class TopkUsers(ScoreUsersOnly):
+    """The same table behind ``topk_users`` as the device ranking orders it (score descending, then the
+    lower item id; excluded items last), computed with numpy; counts its calls."""
+    calls = 0
+
+    def topk_users(self, users, k, exclude_csr=None):
+        self.calls += 1
+        s = self.s[np.asarray(users)].astype(np.float64)
+        if exclude_csr is not None:
+            for r, u in enumerate(users):
+                s[r, exclude_csr.indices[exclude_csr.indptr[u]:exclude_csr.indptr[u + 1]]] = -np.inf
+        return np.argsort(-s, axis=1, kind="stable")[:, :k].astype(np.int64)
