@@ -33,6 +33,9 @@
  *   rg_mf_score_lists / a ragged list of candidate items per user scored, and ranked inside
  *   rg_seg_topk /       each list (re-ranking; the sampled HR / NDCG protocol; no reference
  *   rg_seg_rank         counterpart: it ranks every item)
+ *   rg_seg_mmr /        k entries of each list picked by maximal marginal relevance (relevance
+ *   rg_seg_mean_sim     less similarity to the picks so far), and a list's mean pairwise
+ *                       similarity (no reference counterpart: it stops at argmax)
  *   rg_topk_rows_wide   the first k <= 1024 entries of argsort(-scores) of a score block
  *                                                          spotlight/evaluation.py:115-213
  *   rg_item_sim_topk    the k rows of an embedding table most similar to each query row
@@ -1068,6 +1071,68 @@ int rg_seg_topk(void *stream, const float *scores, const int64_t *list_ptr, cons
                 int64_t n, int32_t k, int32_t *out_pos, float *out_val);
 int rg_seg_rank(void *stream, const float *scores, const int64_t *list_ptr, const int32_t *list_idx,
                 int64_t n, int32_t *out);
+
+/* ------------------------------------------------------------------------------
+ * Diversified re-ranking (rg_diverse.hip): maximal marginal relevance (MMR) inside each
+ * candidate list, and the mean pairwise similarity of a list -- no reference counterpart (it
+ * ranks every item by relevance and stops there).  The lists are the CSR of the candidate
+ * entries above; table [rows][dim] fp32 holds the rows the similarity compares (an item
+ * embedding table), rnorm [rows] its reciprocal norms as rg_row_rnorms writes them, or null
+ * for the inner product.  For two entries e and j of a list
+ *     dot = <table[id_e], table[id_j]>   ONE fmaf chain over the columns 0 .. dim - 1: it
+ *                                        depends on dim alone, so the same pair gives the same
+ *                                        bits at any position, in any list, in any call
+ *     sim = (dot * rnorm[id_e]) * rnorm[id_j]    rnorm given: two fp32 multiplies in that order
+ *         = dot                                   rnorm null
+ *
+ * rg_seg_mmr: k greedy steps per list over key = the key of scores[e] (rg_seg_topk's rule: the
+ * key of a NaN is -inf, -0.0 and +0.0 are one key).
+ *     step 0       selects the list's best entry exactly as rg_seg_topk: key descending, then id
+ *                  ascending, then position ascending;
+ *     step t >= 1  for every unselected entry e, pen_e = max over the selected j of sim(e, j)
+ *                  (the entry after j in the definition above is e), obj_e = key_e where key_e
+ *                  is +-inf and otherwise lam * key_e - (1 - lam) * pen_e -- fp32, 1 - lam
+ *                  rounded once, two multiplies and a subtraction, nothing contracted -- and
+ *                  the best unselected entry by (obj descending, id ascending, position
+ *                  ascending) is selected.
+ * A repeated id is an ordinary entry: its similarity to its twin is computed like any other.
+ *     out_pos[r][t]   the position WITHIN list r selected at step t, -1 past a short list's end;
+ *     out_val[r][t]   the raw score at that position (a NaN stays the NaN it was), -inf in the
+ *                     fill; may be null;
+ *     out_pen[r][t]   pen of that entry when it was selected, 0 at step 0 and in the fill; may
+ *                     be null.
+ * All device, [n][k]; 1 <= k <= RG_SEG_MMR_MAX_K, 0 < lam <= 1 (lam == 1: rg_seg_topk's row),
+ * dim in [1, 256].  Only the first RG_SEG_MMR_MAX_LEN entries of a list are read, never
+ * beyond: a caller refuses longer lists (candidates.py does).  A list's output depends on
+ * that list alone.  One wave per list: the keys, ids and running penalties of entry e stay in
+ * registers of lane e % 64; a step is a butterfly over the lanes and ONE new product per
+ * unselected entry (against the row just selected), so a list costs k dependent steps.  The
+ * list's rows are gathered once into LDS when len * (dim | 1) floats fit the workgroup's stage
+ * (the floats of 128 rows, within [16, 64] KiB: a size that depends on dim alone) and are read
+ * from the table at every step when they do not; both run the same chain on the same values,
+ * so the bits do not depend on the path.  The ids are trusted to be in range, the table and
+ * rnorm to be finite and list_ptr to describe list_idx; everything but the outputs is only
+ * read.  One launch, no workspace, no atomics, nothing allocated.
+ *
+ * rg_seg_mean_sim: out[r] (fp32 [n], device) = the mean of sim over the unordered pairs of
+ * list r's entries, entries with id < 0 skipped (rank_candidates' -1 fill passes straight
+ * in); 0 for a list with fewer than two entries left.  A repeated id is two entries.  The
+ * similarities are added in double in one fixed order (per lane: the earlier entry ascending,
+ * then the later; then a butterfly), divided by the number of pairs and rounded once.  The
+ * same cap on a list's length, the same staging.
+ *
+ * RG_E_ARG (rg_last_error names the reason, no HIP call made, nothing written) on a null
+ * pointer (rnorm, out_val and out_pen alone may be null), dim outside [1, 256], k outside
+ * [1, RG_SEG_MMR_MAX_K], lam outside (0, 1] or NaN, n < 0 or n > 2^31 - 1 (a workgroup per
+ * list); n == 0: RG_OK, no launch.
+ * ---------------------------------------------------------------------------- */
+#define RG_SEG_MMR_MAX_K 32
+#define RG_SEG_MMR_MAX_LEN 1024
+int rg_seg_mmr(void *stream, const float *scores, const int64_t *list_ptr, const int32_t *list_idx,
+               int64_t n, const float *table, const float *rnorm, int32_t dim, float lam, int32_t k,
+               int32_t *out_pos, float *out_val, float *out_pen);
+int rg_seg_mean_sim(void *stream, const int64_t *list_ptr, const int32_t *list_idx, int64_t n,
+                    const float *table, const float *rnorm, int32_t dim, float *out);
 
 /* ------------------------------------------------------------------------------
  * Item-to-item similarity (rg_item_sim.hip): the k rows of an embedding table most similar

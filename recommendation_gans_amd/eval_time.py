@@ -129,6 +129,14 @@ against the full score block + gather + rg_topk_rows, NCF (E = 64) through ``NCF
 ``seg_topk`` against ``NCFEngine.scores_torch`` + ``torch.topk``; the paths alternate in one process,
 device events, min / median and the peak device memory of one call of each.  One JSON line per model
 and shape.
+
+    python -m recommendation_gans_amd.eval_time --metric mmr [--items 26744] [--reps 20]
+
+times diversified re-ranking (maximal marginal relevance) of 100 candidates per user, k = 10, lam = 0.7,
+cosine, at 256 and 4096 users and d in {32, 64, 128}: ``candidates.seg_mmr`` (rg_seg_mmr) against
+``candidates.seg_mmr_torch`` and beside ``seg_topk`` on the same lists; the paths alternate in one
+process, device events, min / median, the peak device memory of one call of each, and the intra-list
+similarity of the picks at lam = 1.0 and 0.7.  One JSON line per shape.
 """
 import argparse
 import contextlib
@@ -764,6 +772,62 @@ def main_candidates(args):
     return out
 
 
+def main_mmr(args):
+    """``--metric mmr``: diversified re-ranking of 100 candidates per user out of ``--items`` items,
+    k = 10, lam = 0.7, cosine, for 256 and 4096 users at d in {32, 64, 128}: ``candidates.seg_mmr``
+    (rg_seg_mmr, one launch) against ``candidates.seg_mmr_torch`` (the padded gather and k rounds of
+    torch ops), and beside them ``seg_topk`` on the same lists (what lam = 1 costs).  Scores, lists,
+    table and reciprocal norms are on the device going in, positions on the device coming out; the
+    paths alternate in one process, median of ``--reps`` device-event measurements, the peak device
+    memory of one call of each, and the intra-list similarity (``seg_mean_sim``) of the picks at
+    lam = 1.0 and 0.7.  One JSON line per shape (profiles/mmr/eval_time_mmr.jsonl holds a run)."""
+    from . import candidates as cand, mf_engine
+    dev = torch.device("cuda:0")
+    I, C, k, lam = args.items, 100, 10, 0.7
+    out = []
+    for d in (32, 64, 128):
+        g = torch.Generator().manual_seed(d)
+        table = (torch.randn(I, d, generator=g) / d ** 0.5).to(dev)
+        rnorm = mf_engine.row_rnorms(table)
+        for n in (256, 4096):
+            rs = np.random.RandomState(n)
+            idx = torch.from_numpy(np.stack([rs.permutation(I)[:C] for _ in range(n)]).astype(np.int32)).to(dev)
+            idx = idx.reshape(-1)
+            ptr = torch.arange(n + 1, dtype=torch.int64, device=dev) * C
+            scores = torch.sigmoid(torch.randn(n * C, generator=g)).to(dev)
+            paths = {"kernel": lambda: cand.seg_mmr(scores, ptr, idx, table, k, lam, rnorm=rnorm, checked=True),
+                     "torch": lambda: cand.seg_mmr_torch(scores, ptr, idx, table, k, lam, rnorm=rnorm),
+                     "seg_topk": lambda: cand.seg_topk(scores, ptr, idx, k, checked=True)}
+            for _ in range(3):                                   # warm-up: code objects, allocator
+                for fn in paths.values():
+                    fn()
+            torch.cuda.synchronize()
+            ts = {name: [] for name in paths}
+            for _ in range(args.reps):                           # alternate the paths
+                for name, fn in paths.items():
+                    ts[name] += timed(fn, 1)
+            a, b = paths["kernel"](), paths["torch"]()
+
+            def ils(pos):
+                picks = torch.gather(idx.view(n, C), 1, pos.to(torch.int64)).reshape(-1).contiguous()
+                p = torch.arange(n + 1, dtype=torch.int64, device=dev) * k
+                return float(cand.seg_mean_sim(p, picks, table, rnorm=rnorm, checked=True).double().mean())
+            r = {"metric": "mmr", "dim": d, "users": n, "items": I, "candidates": C, "k": k, "lam": lam,
+                 "similarity": "cosine", "reps": args.reps, **{name + "_ms": stats(t) for name, t in ts.items()},
+                 **{name + "_peak_mb": _peak_mb(fn, dev) for name, fn in paths.items()},
+                 "gathered_block_mb": 4 * n * C * d / 1e6,
+                 "rows_equal_torch_fp32": float((a == b).all(dim=1).double().mean()),
+                 "intra_list_similarity": {"lam_1.0": ils(cand.seg_mmr(scores, ptr, idx, table, k, 1.0, rnorm=rnorm,
+                                                                      checked=True)), "lam_0.7": ils(a)},
+                 "speedup_vs_torch_median": float(np.median(ts["torch"]) / np.median(ts["kernel"])),
+                 "kernel_over_seg_topk_median": float(np.median(ts["kernel"]) / np.median(ts["seg_topk"]))}
+            print(json.dumps(r), flush=True)
+            out.append(r)
+        del table, rnorm
+        torch.cuda.empty_cache()
+    return out
+
+
 def main_topk_wide(args):
     """``--metric topk_wide``: rg_topk_rows_wide on one score block already on the device, against
     the host path it replaces in the @k metrics above k = 32 (the block to the host, argsort per row)
@@ -1024,7 +1088,7 @@ def main_scores(args):
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--metric", choices=("scores", "mrr", "slates", "pairs", "mf_scores", "mf_topk", "item_sim",
-                                        "gan_recommend", "topk_wide", "gan_score", "fold_in", "candidates"),
+                                        "gan_recommend", "topk_wide", "gan_score", "fold_in", "candidates", "mmr"),
                     default="scores")
     ap.add_argument("--batch", type=int, default=8192)
     ap.add_argument("--users", type=int, default=None)
@@ -1042,7 +1106,8 @@ def main(argv=None):
     return {"scores": main_scores, "mrr": main_mrr, "slates": main_slates, "pairs": main_pairs,
             "mf_scores": main_mf_scores, "mf_topk": main_mf_topk, "item_sim": main_item_sim,
             "gan_recommend": main_gan_recommend, "topk_wide": main_topk_wide,
-            "gan_score": main_gan_score, "fold_in": main_fold_in, "candidates": main_candidates}[args.metric](args)
+            "gan_score": main_gan_score, "fold_in": main_fold_in, "candidates": main_candidates,
+            "mmr": main_mmr}[args.metric](args)
 
 
 if __name__ == "__main__":

@@ -93,11 +93,12 @@ def _exclude_csr_rows(blk, csr, rows):
             torch.as_tensor(sub.indices.astype(np.int64), device=blk.device)] = float("-inf")
 
 
-def _topk_block(blk, k):
+def _topk_block(blk, k, host=True):
     """The k best column ids of a contiguous fp32 score block's rows as (int32 [rows, k] on the
     device, the same on the host), range-checked before anything is indexed with them:
     rg_topk_rows for k <= 32, rg_topk_rows_wide (radix select, the same order) for
-    32 < k <= 1024."""
+    32 < k <= 1024.  ``host=False``: the range is checked on the device, one flag comes down
+    and the second element is None."""
     from . import _lib
     n, cols = blk.shape
     out = torch.empty(n, k, dtype=torch.int32, device=blk.device)
@@ -109,6 +110,10 @@ def _topk_block(blk, k):
         rc = _lib.load().rg_topk_rows_wide(_lib.stream_handle(), _lib.ptr(blk), n, cols, cols, int(k), _lib.ptr(out),
                                            None)
     _lib.check(rc, name)
+    if not host:
+        if out.numel() and bool((out.min() < 0) | (out.max() >= cols)):
+            raise RuntimeError(f"{name} returned an item id outside the table")
+        return out, None
     got = out.cpu().numpy()
     if got.size and (got.min() < 0 or got.max() >= cols):
         raise RuntimeError(f"{name} returned an item id outside the table")
@@ -665,6 +670,107 @@ class ImplicitFactorizationModel:
             out[s:e] = cand.seg_rank(sc, p, i, checked=True).cpu().numpy()
         return out
 
+    def _similarity(self, metric, space):
+        """(item table, reciprocal norms or None) behind the diversified rankings: ``similar_items``'
+        table and metric, the norms computed once per call."""
+        table = self._item_table(space).contiguous()
+        return table, (mf_engine.row_rnorms(table) if metric == "cosine" else None)
+
+    def diversify_candidates(self, user_ids, candidates, k=10, lam=0.7, metric="cosine", space=None,
+                             return_scores=False):
+        """``rank_candidates`` with diversity: k of each user's candidate items picked greedily by
+        maximal marginal relevance -- the best score first, then at every step the candidate with the
+        largest ``lam * score - (1 - lam) * (its largest similarity to an item already picked)``,
+        ties to the lower item id, then the lower position.  ``(len(user_ids), k)`` int64 item ids on
+        the host in pick order, -1 where a list has fewer than k entries, with ``return_scores`` also
+        their float32 scores (the model's, not the objective; -inf there).  ``lam=1`` is
+        ``rank_candidates``; a smaller ``lam`` trades relevance for variety.
+
+        ``candidates`` as in ``score_candidates``, whose scores are the relevance (MF, NCF, NeuMF);
+        the similarity is ``similar_items``': ``metric`` "cosine" or "dot" over the item table
+        ``space`` names (NeuMF: "mf", the default, or "mlp"; MF and NCF: None), the reciprocal norms
+        computed once per call.  Scored on the device, then one launch per block of 4096 users
+        (rg_seg_mmr, ``candidates.seg_mmr``); only ids and scores come down.  ValueError for an id
+        outside the model, k outside [1, 32], lam outside (0, 1], a list of more than 1024
+        candidates, a number of lists other than ``len(user_ids)``, an unknown ``metric`` or an
+        unknown ``space``."""
+        from . import candidates as cand
+        what = "diversify_candidates"
+        k, lam = cand._mmr_k_lam(k, lam, what)
+        self._check_metric(metric)
+        n, ptr, blocks = self._candidate_blocks(user_ids, candidates, what)
+        if n and np.diff(ptr).max() > cand.SEG_MMR_MAX_LEN:
+            raise ValueError(f"{what}: a list is longer than {cand.SEG_MMR_MAX_LEN} entries")
+        space = self._check_space(space)
+        ids = np.full((n, k), -1, dtype=np.int64)
+        scores = np.full((n, k), -np.inf, dtype=np.float32)
+        if ptr[-1] == 0:
+            return (ids, scores) if return_scores else ids
+        table, rnorm = self._similarity(metric, space)
+        for s, e, p, i, sc in blocks:
+            if not i.numel():
+                continue
+            pos, val = cand.seg_mmr(sc, p, i, table, k, lam, rnorm=rnorm, return_values=True, checked=True)
+            at = (p[:-1, None] + pos.clamp(min=0)).clamp(max=i.numel() - 1)
+            ids[s:e] = torch.where(pos >= 0, i[at].to(torch.int64), -1).cpu().numpy()
+            if return_scores:
+                scores[s:e] = val.cpu().numpy()
+        return (ids, scores) if return_scores else ids
+
+    def recommend_diverse(self, user_ids, k=10, pool=100, lam=0.7, exclude=None, metric="cosine", space=None,
+                          return_scores=False):
+        """``recommend`` with diversity: for each user the ``pool`` best items are retrieved and k of
+        them are picked by maximal marginal relevance (``diversify_candidates``' rule over that
+        pool).  ``(len(user_ids), k)`` int64 item ids on the host in pick order, with
+        ``return_scores`` also their float32 scores.  ``lam=1`` returns ``recommend``'s ids and score
+        bits; ``exclude`` as in ``recommend``; ``metric`` and ``space`` as in ``similar_items``.
+
+        4096 users at a time, all on the device: the score block (``_device_scores``), -inf over the
+        excluded entries, the pool's ids by ``_topk_block`` (rg_topk_rows, rg_topk_rows_wide beyond
+        32), their scores gathered from the block, then rg_seg_mmr over the regular (users, pool)
+        lists (``candidates.seg_mmr``); only ids and scores come down.  The block is always built:
+        there is no fused path here.  ValueError for an id outside the model, k outside
+        [1, min(32, num_items)], pool outside [k, min(1024, num_items)], lam outside (0, 1], an
+        ``exclude`` of another shape, an unknown ``metric`` or an unknown ``space``."""
+        from . import candidates as cand
+        what = "recommend_diverse"
+        if not self._initialized:
+            raise RuntimeError(f"{what} needs a fitted model")
+        users = np.asarray(user_ids, dtype=np.int64).reshape(-1)
+        n, num_items = len(users), self._num_items
+        if int(k) != k or k < 1 or k > min(cand.SEG_MMR_MAX, num_items):
+            raise ValueError(f"k must be in [1, min({cand.SEG_MMR_MAX}, num_items)]")
+        k, lam = cand._mmr_k_lam(k, lam, what)
+        if int(pool) != pool or pool < k or pool > min(cand.SEG_MMR_MAX_LEN, num_items):
+            raise ValueError(f"pool must be in [k, min({cand.SEG_MMR_MAX_LEN}, num_items)]")
+        pool = int(pool)
+        self._check_metric(metric)
+        if n and (users.min() < 0 or users.max() >= self._num_users):
+            raise ValueError("user id outside [0, num_users)")
+        csr = None
+        if exclude is not None:
+            csr = exclude.tocsr()
+            if csr.shape != (self._num_users, num_items):
+                raise ValueError(f"exclude has shape {csr.shape}, the model {(self._num_users, num_items)}")
+        space = self._check_space(space)
+        ids = np.empty((n, k), dtype=np.int64)
+        scores = np.empty((n, k), dtype=np.float32)
+        if n == 0:
+            return (ids, scores) if return_scores else ids
+        table, rnorm = self._similarity(metric, space)
+        for s in range(0, n, 4096):
+            ub, blk = _score_block(self, users[s:s + 4096])
+            _exclude_csr_rows(blk, csr, ub)
+            cands = _topk_block(blk, pool, host=False)[0]        # checked: never index the block with a bad id
+            sc = torch.gather(blk, 1, cands.to(torch.int64)).reshape(-1)
+            p = torch.arange(len(ub) + 1, dtype=torch.int64, device=blk.device) * pool
+            pos, val = cand.seg_mmr(sc, p, cands.reshape(-1), table, k, lam, rnorm=rnorm, return_values=True,
+                                    checked=True)
+            ids[s:s + len(ub)] = torch.gather(cands, 1, pos.to(torch.int64)).cpu().numpy()   # pool >= k: no fill
+            if return_scores:
+                scores[s:s + len(ub)] = val.cpu().numpy()
+        return (ids, scores) if return_scores else ids
+
     def _fold_in_device(self, histories, steps, lr, n_neg, l2, random_state, return_loss):
         """``fold_in_users`` up to the device results: (indptr, indices, (W, b[, loss]) on the device)."""
         if not self._initialized:
@@ -755,6 +861,22 @@ class ImplicitFactorizationModel:
             return self._tables()[1]
         return self._engine.mf_w[1] if space == "mf" else self._engine.item_w
 
+    @staticmethod
+    def _check_metric(metric):
+        if metric not in mf_engine.SIM_METRICS:
+            raise ValueError(f"unknown metric {metric!r}: one of {mf_engine.SIM_METRICS}")
+
+    def _check_space(self, space):
+        """``space`` as ``_item_table`` takes it: NeuMF's default is "mf"; ValueError for a name the
+        model does not have."""
+        neumf = self._kind != "mf" and self._engine.neumf
+        if neumf and space is None:
+            space = "mf"
+        if space not in (("mf", "mlp") if neumf else (None,)):
+            raise ValueError(f"unknown space {space!r}: NeuMF has 'mf' (the GMF item table, the default) and 'mlp' "
+                             "(the tower's); MF and NCF have one item table and take None")
+        return space
+
     def similar_items(self, item_ids, k=10, metric="cosine", include_self=False, space=None, return_scores=False):
         """The k items most similar to each of ``item_ids`` ("more like this"): ``(len(item_ids), k)``
         int64 item ids on the host in rank order (higher similarity first, then the lower item id),
@@ -771,18 +893,12 @@ class ImplicitFactorizationModel:
         that this path never builds."""
         items = np.asarray(item_ids, dtype=np.int64).reshape(-1)
         k, n, num_items = int(k), len(items), self._num_items
-        if metric not in mf_engine.SIM_METRICS:
-            raise ValueError(f"unknown metric {metric!r}: one of {mf_engine.SIM_METRICS}")
+        self._check_metric(metric)
         if k < 1 or k > min(32, num_items - (0 if include_self else 1)):
             raise ValueError("k must be in [1, min(32, num_items - 1)] (num_items with include_self)")
         if n and (items.min() < 0 or items.max() >= num_items):
             raise ValueError("item id outside [0, num_items)")
-        neumf = self._kind != "mf" and self._engine.neumf
-        if neumf and space is None:
-            space = "mf"
-        if space not in (("mf", "mlp") if neumf else (None,)):
-            raise ValueError(f"unknown space {space!r}: NeuMF has 'mf' (the GMF item table, the default) and 'mlp' "
-                             "(the tower's); MF and NCF have one item table and take None")
+        space = self._check_space(space)
         ids = np.empty((n, k), dtype=np.int64)
         sims = np.empty((n, k), dtype=np.float32)
         if n == 0:

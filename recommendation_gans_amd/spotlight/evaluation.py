@@ -343,6 +343,48 @@ def sampled_hit_ndcg(model, test, train=None, n_negatives=99, k=10, random_state
     return float(np.mean(hit)), float(np.mean(gain))
 
 
+def intra_list_similarity(model, item_lists, metric="cosine", space=None):
+    """The intra-list similarity of recommendation lists or slates: per list the mean similarity over
+    the unordered pairs of its items, then the mean over the lists -- lower is more diverse.
+    ``item_lists``: an ``(n, k)`` integer array or a list of id sequences; a negative id (the -1 fill
+    of ``rank_candidates`` / ``diversify_candidates``) is skipped, a list with fewer than two items
+    counts 0.  The items are compared in ``model``'s item space -- any fitted
+    ImplicitFactorizationModel, whatever produced the lists (``recommend*`` outputs and cGAN slates
+    alike) -- with ``similar_items``' ``metric`` ("cosine" / "dot") and ``space``.  Computed on the
+    device (rg_seg_mean_sim, ``candidates.seg_mean_sim``): the lists go up, one value per list comes
+    down.  ValueError for no lists, a list of more than 1024 items, ids that are not integers, an id
+    at or beyond ``num_items``, an unknown ``metric`` or an unknown ``space``."""
+    import torch
+    from .. import candidates as cand
+    from .. import mf_engine
+    if isinstance(item_lists, np.ndarray) and item_lists.ndim == 2:
+        lists = list(item_lists)
+    else:
+        lists = [np.asarray(r).reshape(-1) for r in item_lists]
+    if not len(lists):
+        raise ValueError("intra_list_similarity: no lists")
+    if any(len(r) and np.asarray(r).dtype.kind not in "iu" for r in lists):
+        raise ValueError("intra_list_similarity: the lists must hold integer item ids")
+    ptr = np.zeros(len(lists) + 1, dtype=np.int64)
+    np.cumsum([len(r) for r in lists], out=ptr[1:])
+    if np.diff(ptr).max() > cand.SEG_MMR_MAX_LEN:
+        raise ValueError(f"intra_list_similarity: a list is longer than {cand.SEG_MMR_MAX_LEN} items")
+    idx = np.concatenate(lists).astype(np.int64) if ptr[-1] else np.zeros(0, dtype=np.int64)
+    if len(idx) and idx.max() >= model._num_items:
+        raise ValueError("intra_list_similarity: item id outside [0, num_items)")
+    model._check_metric(metric)
+    space = model._check_space(space)
+    if not ptr[-1]:
+        return 0.0
+    table = model._item_table(space).contiguous()
+    rnorm = mf_engine.row_rnorms(table) if metric == "cosine" else None
+    dev = table.device
+    sims = cand.seg_mean_sim(torch.as_tensor(ptr, device=dev), torch.as_tensor(np.maximum(idx, -1).astype(np.int32),
+                                                                               device=dev),
+                             table, rnorm=rnorm, checked=True)
+    return float(sims.double().mean().item())
+
+
 def evaluate_popItems(item_popularity, test, k=10):
     test = test.tocsr()
     pop = np.asarray(getattr(item_popularity, "values", item_popularity))
