@@ -30,6 +30,9 @@
  *   rg_mf_topk_users    the k best items of those users, scored, excluded and ranked in LDS
  *   rg_mf_fold_in_users rows and biases of NEW users fitted against the frozen item tables
  *                       (the model's loss, Adam; no reference counterpart: it retrains)
+ *   rg_als_gram /       implicit ALS: the Gram matrix of a table and one half-step of
+ *   rg_als_solve_rows   confidence-weighted least squares by per-row conjugate gradients
+ *                       (no reference counterpart: it trains by sampled SGD only)
  *   rg_mf_score_lists / a ragged list of candidate items per user scored, and ranked inside
  *   rg_seg_topk /       each list (re-ranking; the sampled HR / NDCG protocol; no reference
  *   rg_seg_rank         counterpart: it ranks every item)
@@ -1014,6 +1017,64 @@ int rg_mf_fold_in_users(void *stream, const float *item_w, const float *item_b, 
                         const int32_t *neg_idx, int32_t n_neg, int64_t n_users, int32_t loss,
                         const rg_opt_t *opt, const float *step_coef, int32_t steps, float *user_w,
                         float *user_b, float *loss_out);
+
+/* ------------------------------------------------------------------------------
+ * Implicit ALS (rg_als.hip): alternating least squares with confidence weights (Hu, Koren,
+ * Volinsky 2008) on a pair of MF tables without biases -- no reference counterpart (the reference
+ * trains by sampled SGD only).  A half-step solves every row of one table against the other,
+ * FROZEN table; the item half-step is the same call with the transposed CSR and the tables
+ * swapped.  Everything is fp32 on the device; no atomics anywhere, so every output repeats bit
+ * for bit from run to run.
+ *
+ * rg_als_gram: out_G [dim][dim] = table^T table + lam I for table [n_rows][dim].  Per-block
+ * partials over 1024 rows each (ascending rows) go to workspace_dev, rg_als_gram_workspace_len
+ * (n_rows, dim) floats (-1 for arguments the call refuses), and are added in ascending block
+ * order; out_G is symmetric bit for bit.  n_rows == 0: lam I.  RG_E_ARG (no HIP call, nothing
+ * written) on a null table, workspace_dev or out_G, dim outside [1, 128], n_rows < 0 or above
+ * 1024 (2^31 - 1), or a lam that is negative or not finite.
+ *
+ * rg_als_solve_rows: for the k-th of the call's n_rows rows, u = rows[k] (rows null: u = k; a
+ * row id may appear once), with list N = row_idx[row_ptr[u] .. row_ptr[u + 1]) (device, int64
+ * offsets, int32 ids into other_table; duplicates count as given), values v_i = row_val[e]
+ * (row_val null: 1), c_i = 1 + alpha v_i, y_i = other_table[i] and G as given (rg_als_gram of
+ * other_table; it must be symmetric, the kernel reads G[j][i] for G[i][j]):
+ *     A = G + sum_{i in N} (c_i - 1) y_i y_i^T          b = sum_{i in N} c_i y_i
+ * x = x_inout[u] takes cg_steps iterations of conjugate gradients on A x = b from its value on
+ * entry (A is never formed: A p = G p + sum_i (c_i - 1) (y_i . p) y_i):
+ *     r = b - A x;  p = r;  rs = r.r
+ *     repeat cg_steps times:
+ *         stop if rs == 0;  Ap = A p;  pAp = p.Ap;  stop if not pAp > 0     (no tolerance)
+ *         a = rs / pAp;  x += a p;  r -= a Ap;  rn = r.r;  p = r + (rn / rs) p;  rs = rn
+ * and is written back.  A row with an empty list is set to exactly zero (the exact solve).
+ * cg_steps == 0 leaves the rows with a list untouched and still zeroes the empty ones.
+ * loss_out (optional, indexed by u like x_inout): at the returned x,
+ *     x^T G x + sum_{i in N} ((c_i - 1) (x.y_i)^2 - 2 c_i (x.y_i) + c_i)
+ * -- with G = Y^T Y (lam = 0) the row's term of the ALS objective without its lam terms, with
+ * G = Y^T Y + lam I that plus lam |x|^2; 0 for an empty row.
+ *
+ * Two paths, chosen per row by the length of its list alone.  Shorter than
+ * rg_als_long_row_len(): the row is owned by one group of lanes (the pair kernel's lane x float4
+ * row layout; 64 / lanes rows per wave) for all passes, x, r, p and A p in registers, G staged
+ * once per workgroup in LDS, p broadcast through LDS for G p, the list walked in ascending order.
+ * Otherwise one workgroup takes the row: its lane groups each sum one contiguous chunk of the list
+ * and the partial sums are added through LDS in chunk order.  A row's output bits depend on its
+ * own list, values and start and on G alone: not on its place in the call, on n_rows or on the
+ * other rows.  16-byte loads when dim is 8, 16, 32, 64 or 128 and other_table and x_inout are
+ * 16-byte aligned.  Ids are trusted: row_ptr must ascend, every id lie inside other_table and
+ * every row id inside row_ptr / x_inout.
+ * RG_E_ARG (rg_last_error names the reason, no HIP call made, nothing written) on a null
+ * other_table, G, row_ptr or x_inout, dim outside [1, 128], cg_steps outside [0, 64], an alpha
+ * that is negative or not finite, n_rows < 0, or (with n_rows > 0) a null row_idx.
+ * n_rows == 0: RG_OK, no launch.
+ * ---------------------------------------------------------------------------- */
+int32_t rg_als_long_row_len(void);
+int64_t rg_als_gram_workspace_len(int64_t n_rows, int32_t dim);
+int rg_als_gram(void *stream, const float *table, int64_t n_rows, int32_t dim, float lam,
+                float *workspace_dev, float *out_G);
+int rg_als_solve_rows(void *stream, const float *other_table, const float *G, int32_t dim,
+                      const int64_t *row_ptr, const int32_t *row_idx, const float *row_val,
+                      float alpha, const int64_t *rows, int64_t n_rows, int32_t cg_steps,
+                      float *x_inout, float *loss_out);
 
 /* ------------------------------------------------------------------------------
  * Candidate lists (rg_cand.hip): score a ragged list of items per user and rank INSIDE each

@@ -137,6 +137,20 @@ cosine, at 256 and 4096 users and d in {32, 64, 128}: ``candidates.seg_mmr`` (rg
 ``candidates.seg_mmr_torch`` and beside ``seg_topk`` on the same lists; the paths alternate in one
 process, device events, min / median, the peak device memory of one call of each, and the intra-list
 similarity of the picks at lam = 1.0 and 0.7.  One JSON line per shape.
+
+    python -m recommendation_gans_amd.eval_time --metric als [--users 138493] [--items 26744] [--reps 20]
+
+times implicit ALS (``als.py``: rg_als_gram, rg_als_solve_rows) on a synthetic ML-20M-shaped matrix,
+``--users`` x ``--items`` with 20 M interactions and Zipf-skewed item popularity (exponent 0.5: the
+most popular item has ~60 k users, so the item half-step has workgroup-per-row lists beside a median
+of a few hundred), at d in {32, 64, 128} and cg_steps = 3: one full sweep, and separately ``gram``,
+the user half-step, the item half-step, and the item half-step's rows at or above
+``rg_als_long_row_len()`` alone (the long path's share).  The half-steps alternate with
+``als.solve_rows_torch`` on the same inputs in the same process (rows sorted by length, blocks of at
+most ``block_elems`` padded elements; ``torch_reps`` repetitions).  Device events, min / median, the
+largest difference of the two results, and the kernel's distance from its two bounds:
+(cg_steps + 1) nnz d 4 gathered bytes at 8 TB/s, and its flops at the fp32 vector peak.  One JSON
+line per d.
 """
 import argparse
 import contextlib
@@ -665,6 +679,100 @@ def main_fold_in(args):
     return out
 
 
+def main_als(args):
+    """``--metric als``: one ALS sweep and its parts (gram, the two half-steps, the long rows of the
+    item half-step alone) on a synthetic ML-20M-shaped matrix, the half-steps against
+    als.solve_rows_torch on the same inputs; see the module docstring.  ``bytes_bound_ms``: (cg_steps
+    + 1) nnz d 4 gathered bytes at 8 TB/s; ``flops_bound_ms``: per pass 4 d flops per entry (the dot
+    and the accumulation) and 2 d^2 per row (G p), at 157.3 TFLOP/s."""
+    from . import als
+    dev = torch.device("cuda:0")
+    U, I, nnz, cg, lam, alpha = args.users, args.items, args.nnz, 3, 0.01, 40.0
+    rs = np.random.RandomState(0)
+    pop = 1.0 / np.sqrt(np.arange(1, I + 1))
+    items = rs.choice(I, size=nnz, p=pop / pop.sum()).astype(np.int32)
+    users = rs.randint(0, U, nnz).astype(np.int32)
+    csr_u = als.interactions_csr(users, items, None, U)
+    csr_i = als.interactions_csr(items, users, None, I)
+    T = als.long_row_len()
+    block_elems, torch_reps = 1 << 26, min(args.reps, 3)
+    out = []
+    for d in (32, 64, 128):
+        g = torch.Generator().manual_seed(d)
+        X0 = (torch.randn(U, d, generator=g) / d).to(dev)
+        Y0 = (torch.randn(I, d, generator=g) / d).to(dev)
+        sides = {}
+        for name, (p_, i_, _), own, other in (("user", csr_u, X0, Y0), ("item", csr_i, Y0, X0)):
+            pd, idd = torch.from_numpy(p_).to(dev), torch.from_numpy(i_).to(dev)
+            order = als.rows_by_length(p_).to(dev)
+            lens = np.diff(p_)
+            long_rows = torch.from_numpy(np.flatnonzero(lens >= T).astype(np.int64)).to(dev)
+            sides[name] = dict(ptr=pd, idx=idd, order=order, own=own, other=other, lens=lens, long_rows=long_rows)
+
+        def half(name, x, torch_path=False, rows=None):
+            s_ = sides[name]
+            G = als.gram(s_["other"], lam)
+            fn = als.solve_rows_torch if torch_path else als.solve_rows
+            kw = dict(block_elems=block_elems) if torch_path else {}
+            return fn(s_["other"], G, s_["ptr"], s_["idx"], None, alpha, cg, x, rows=s_["order"] if rows is None else rows,
+                      **kw)
+
+        def sweep():
+            X, Y = X0.clone(), Y0.clone()
+            als.solve_rows(Y, als.gram(Y, lam), sides["user"]["ptr"], sides["user"]["idx"], None, alpha, cg, X,
+                           rows=sides["user"]["order"])
+            als.solve_rows(X, als.gram(X, lam), sides["item"]["ptr"], sides["item"]["idx"], None, alpha, cg, Y,
+                           rows=sides["item"]["order"])
+
+        r = {"metric": "als", "dim": d, "users": U, "items": I, "nnz": nnz, "cg_steps": cg, "lam": lam, "alpha": alpha,
+             "reps": args.reps, "torch_reps": torch_reps, "torch_block_elems": block_elems, "long_row_len": T}
+        for _ in range(2):
+            sweep()
+        r["sweep_ms"] = stats(timed(sweep, args.reps))
+        r["gram_users_ms"] = stats(timed(lambda: als.gram(X0, lam), args.reps))
+        r["gram_items_ms"] = stats(timed(lambda: als.gram(Y0, lam), args.reps))
+        for name in ("user", "item"):
+            s_ = sides[name]
+            xk, xt = s_["own"].clone(), s_["own"].clone()
+            half(name, xk)
+            half(name, xt, torch_path=True)
+            torch.cuda.synchronize()
+            r[f"{name}_max_abs_diff"] = float((xk - xt).abs().max())
+            r[f"{name}_max_abs"] = float(xt.abs().max())
+            t_new, t_old = [], []
+            for k in range(args.reps):                        # alternate the two paths
+                xk.copy_(s_["own"])
+                t_new += timed(lambda: half(name, xk), 1)
+                if k < torch_reps:
+                    xt.copy_(s_["own"])
+                    t_old += timed(lambda: half(name, xt, torch_path=True), 1)
+            n_rows, n_e = len(s_["lens"]), int(s_["lens"].sum())
+            bytes_b = (cg + 1) * n_e * d * 4 / 8e12 * 1e3
+            flops_b = (cg + 1) * (4.0 * d * n_e + 2.0 * d * d * n_rows) / 157.3e12 * 1e3
+            med = float(np.median(t_new))
+            r[f"{name}_half_ms"] = stats(t_new)
+            r[f"{name}_half_torch_ms"] = stats(t_old)
+            r[f"{name}_torch_over_kernel"] = float(np.median(t_old) / med)
+            r[f"{name}_bytes_bound_ms"], r[f"{name}_flops_bound_ms"] = bytes_b, flops_b
+            r[f"{name}_kernel_over_bound"] = med / max(bytes_b, flops_b)
+            r[f"{name}_longest_row"] = int(s_["lens"].max())
+            r[f"{name}_long_rows"] = int(s_["long_rows"].numel())
+            r[f"{name}_long_entries_share"] = float(s_["lens"][s_["lens"] >= T].sum() / max(n_e, 1))
+            if s_["long_rows"].numel():
+                t_long = []
+                for _ in range(args.reps):
+                    xk.copy_(s_["own"])
+                    t_long += timed(lambda: half(name, xk, rows=s_["long_rows"]), 1)
+                r[f"{name}_long_rows_alone_ms"] = stats(t_long)
+                r[f"{name}_long_share_of_half"] = float(np.median(t_long) / med)
+            del xk, xt
+        print(json.dumps(r), flush=True)
+        out.append(r)
+        del X0, Y0, sides
+        torch.cuda.empty_cache()
+    return out
+
+
 def _peak_mb(fn, dev):
     """Peak device memory of one call of fn above what was allocated before it, in MB."""
     torch.cuda.synchronize()
@@ -1088,7 +1196,8 @@ def main_scores(args):
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--metric", choices=("scores", "mrr", "slates", "pairs", "mf_scores", "mf_topk", "item_sim",
-                                        "gan_recommend", "topk_wide", "gan_score", "fold_in", "candidates", "mmr"),
+                                        "gan_recommend", "topk_wide", "gan_score", "fold_in", "candidates", "mmr",
+                                        "als"),
                     default="scores")
     ap.add_argument("--batch", type=int, default=8192)
     ap.add_argument("--users", type=int, default=None)
@@ -1097,17 +1206,18 @@ def main(argv=None):
     ap.add_argument("--reps", type=int, default=None)
     ap.add_argument("--big", type=int, default=0)
     ap.add_argument("--test-users", type=int, default=4096)
+    ap.add_argument("--nnz", type=int, default=20_000_000)
     args = ap.parse_args(argv)
     slates = args.metric == "slates"             # its own defaults: every ML-20M user, 5 repetitions
     if args.users is None:
-        args.users = ML20M_USERS if slates else 256
+        args.users = ML20M_USERS if slates else 138493 if args.metric == "als" else 256
     if args.reps is None:
         args.reps = 5 if slates or args.metric == "pairs" else 20
     return {"scores": main_scores, "mrr": main_mrr, "slates": main_slates, "pairs": main_pairs,
             "mf_scores": main_mf_scores, "mf_topk": main_mf_topk, "item_sim": main_item_sim,
             "gan_recommend": main_gan_recommend, "topk_wide": main_topk_wide,
             "gan_score": main_gan_score, "fold_in": main_fold_in, "candidates": main_candidates,
-            "mmr": main_mmr}[args.metric](args)
+            "mmr": main_mmr, "als": main_als}[args.metric](args)
 
 
 if __name__ == "__main__":

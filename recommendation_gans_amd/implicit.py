@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from . import _mtstate
+from . import als
 from . import mf_engine
 from .mf_engine import MFEngine
 from .ncf_engine import NCFEngine
@@ -225,6 +226,8 @@ class ImplicitFactorizationModel:
         self.best_validation = None
         self.model_name = model_name
         self.best_epoch = -1
+        self.als_losses = None         # fit_als: the objective after every sweep
+        self._als = None               # fit_als: (regularization, alpha, cg_steps), fold_in_users_als' defaults
         # additive: data-parallel training over world_size processes (one per GPU, under
         # torchrun, torch.distributed initialised by the caller before any GPU work); the
         # reference's single process at batch world_size * batch_size, reproduced by the
@@ -814,7 +817,103 @@ class ImplicitFactorizationModel:
         out = self._fold_in_device(histories, steps, lr, n_neg, l2, random_state, return_loss)[2]
         return tuple(t.cpu().numpy() for t in out)
 
-    def recommend_for_histories(self, histories, k=10, exclude_history=True, return_scores=False, **fold_kwargs):
+    def fit_als(self, train_set, iterations=15, regularization=0.01, alpha=40.0, cg_steps=3, verbose=False):
+        """Fit the MF tables by implicit alternating least squares (Hu, Koren, Volinsky 2008) instead
+        of the sampled SGD step of ``fit``: ``iterations`` sweeps of a user and an item half-step, each
+        row taking ``cg_steps`` conjugate-gradient iterations on its confidence-weighted normal
+        equations (``als.als_sweeps``: rg_als_gram, rg_als_solve_rows).  No negatives and no random
+        draws: it works on a default-constructed model, and the result is reproducible bit for bit.
+
+        Confidence is ``1 + alpha * weight`` with ``train_set.weights`` (1 without weights, duplicates
+        of a pair counted as given); ``ratings`` are ignored.  The start is the model's current tables
+        (``BilinearNet``'s own init on a fresh model).  The result is installed with zero biases, so
+        ``sigmoid(x.y)`` ranks like ``x.y`` and ``recommend``, ``similar_items``, the candidate and
+        re-ranking calls and the ranking metrics work on it unchanged; a later ``fit`` continues from
+        these tables.  ``als_losses`` holds the ALS objective after every sweep (logged with
+        ``verbose``); ``regularization``, ``alpha`` and ``cg_steps`` become ``fold_in_users_als``'
+        defaults.  MF only (NotImplementedError for NCF, NeuMF and world_size > 1); ValueError for
+        regularization <= 0, alpha < 0, iterations < 1, cg_steps outside [1, 64] or embedding_dim >
+        128."""
+        iterations, cg_steps = int(iterations), int(cg_steps)
+        if not (0.0 < float(regularization) < float("inf")):
+            raise ValueError("fit_als: regularization must be finite and > 0")
+        if not (0.0 <= float(alpha) < float("inf")):
+            raise ValueError("fit_als: alpha must be finite and >= 0")
+        if iterations < 1:
+            raise ValueError("fit_als: iterations must be >= 1")
+        if cg_steps < 1 or cg_steps > als.MAX_CG_STEPS:
+            raise ValueError(f"fit_als: cg_steps must be in [1, {als.MAX_CG_STEPS}]")
+        if self._world > 1:
+            raise NotImplementedError("fit_als is single-process")
+        if not self._initialized:
+            if self._representation is None and self._embedding_dim > als.MAX_DIM:
+                raise ValueError(f"fit_als: embedding_dim must be at most {als.MAX_DIM}")
+            self._initialize(train_set)
+        if self._kind != "mf":
+            raise NotImplementedError("fit_als is implemented for the matrix-factorization model (BilinearNet)")
+        if self._embedding_dim > als.MAX_DIM:
+            raise ValueError(f"fit_als: embedding_dim must be at most {als.MAX_DIM}")
+        self._check_input(train_set.user_ids, train_set.item_ids)
+        self.train_set = train_set
+        w = getattr(train_set, "weights", None)
+        csr_u = als.interactions_csr(train_set.user_ids, train_set.item_ids, w, self._num_users)
+        csr_i = als.interactions_csr(train_set.item_ids, train_set.user_ids, w, self._num_items)
+        user_w, item_w, user_b, item_b = self._engine.params()
+        X, Y = user_w.detach().clone().contiguous(), item_w.detach().clone().contiguous()
+        self.als_losses = []
+        als.als_sweeps(X, Y, csr_u, csr_i, iterations=iterations, lam=float(regularization), alpha=float(alpha),
+                       cg_steps=cg_steps, losses=self.als_losses)
+        if verbose:
+            for s, v in enumerate(self.als_losses):
+                logging.info("ALS sweep {}: objective {:14.6f}".format(s, v))
+        tables = [X, Y, torch.zeros_like(user_b), torch.zeros_like(item_b)]
+        self._engine.set_params(*tables)
+        self._full_tables = None
+        self._load_into_net(tables)
+        self._als = (float(regularization), float(alpha), cg_steps)
+        return self
+
+    def _fold_in_als_device(self, histories, regularization, alpha, cg_steps):
+        """``fold_in_users_als`` up to the device results: (indptr, indices, (W, b) on the device)."""
+        if not self._initialized:
+            raise RuntimeError("fold_in_users_als needs a fitted model")
+        if self._kind != "mf":
+            raise NotImplementedError("fold-in is implemented for the matrix-factorization model (BilinearNet)")
+        reg0, alpha0, _ = self._als if self._als is not None else (0.01, 40.0, None)
+        reg = reg0 if regularization is None else float(regularization)
+        alpha = alpha0 if alpha is None else float(alpha)
+        dim = self._embedding_dim
+        cg_steps = min(dim, 16) if cg_steps is None else int(cg_steps)
+        if not (0.0 < reg < float("inf")):
+            raise ValueError("fold_in_users_als: regularization must be finite and > 0")
+        if not (0.0 <= alpha < float("inf")):
+            raise ValueError("fold_in_users_als: alpha must be finite and >= 0")
+        if cg_steps < 1 or cg_steps > als.MAX_CG_STEPS:
+            raise ValueError(f"fold_in_users_als: cg_steps must be in [1, {als.MAX_CG_STEPS}]")
+        if dim > als.MAX_DIM:
+            raise ValueError(f"fold_in_users_als: embedding_dim must be at most {als.MAX_DIM}")
+        ptr, idx = _histories_csr(histories, self._num_items)
+        _, item_w, _, _ = self._tables()
+        dev = self._engine.device
+        W = torch.zeros(len(ptr) - 1, dim, dtype=torch.float32, device=dev)
+        if len(ptr) > 1:
+            Y = item_w.detach().contiguous()
+            als.solve_rows(Y, als.gram(Y, reg), ptr, idx, None, alpha, cg_steps, W)
+        return ptr, idx, (W, torch.zeros(len(ptr) - 1, dtype=torch.float32, device=dev))
+
+    def fold_in_users_als(self, histories, regularization=None, alpha=None, cg_steps=None):
+        """Factors for users that were NOT in the training set by one ALS user half-step from zero
+        against the frozen item table (the closed-form counterpart of ``fold_in_users``; meant for a
+        model fitted with ``fit_als``, whose item biases are zero): ``cg_steps`` conjugate-gradient
+        iterations per user, ``min(dim, 16)`` by default, in one launch.  ``regularization`` and
+        ``alpha`` default to those of ``fit_als`` (0.01 and 40 on a model fitted otherwise).
+        ``histories`` as in ``fold_in_users``; a user with an empty history gets the zero row.
+        Returns host arrays ``(factors [n, dim], biases [n])`` float32, the biases zero."""
+        out = self._fold_in_als_device(histories, regularization, alpha, cg_steps)[2]
+        return tuple(t.cpu().numpy() for t in out)
+
+    def recommend_for_histories(self, histories, k=10, exclude_history=True, return_scores=False, method="adam",
+                                **fold_kwargs):
         """``recommend`` for users the model has never seen: their rows are folded in from
         ``histories`` (``fold_in_users``; ``fold_kwargs`` are its ``steps``, ``lr``, ``n_neg``, ``l2``
         and ``random_state``) and ranked like known users -- ``(len(histories), k)`` int64 item ids on
@@ -823,17 +922,28 @@ class ImplicitFactorizationModel:
         items have the score -inf and are only returned, by id, to a row with fewer than k other
         items.  One fold-in for all rows, then 4096 rows at a time: ``mf_engine.score_users_block``
         with the folded rows as the user table, -inf over the block's histories, rg_topk_rows, and the
-        scores gathered from the block at the returned ids.  ValueError for k < 1 or
-        k > min(32, num_items), as ``recommend``."""
+        scores gathered from the block at the returned ids.  ``method="als"`` folds in with
+        ``fold_in_users_als`` instead (``fold_kwargs`` are then its ``regularization``, ``alpha`` and
+        ``cg_steps``); another name is a ValueError.  ValueError for k < 1 or k > min(32, num_items),
+        as ``recommend``."""
         k, num_items = int(k), self._num_items
         if self._initialized and (k < 1 or k > min(32, num_items)):
             raise ValueError("k must be in [1, min(32, num_items)]")
-        extra = set(fold_kwargs) - {"steps", "lr", "n_neg", "l2", "random_state"}
+        if method not in ("adam", "als"):
+            raise ValueError(f"recommend_for_histories: unknown method {method!r}: 'adam' or 'als'")
+        names = {"steps", "lr", "n_neg", "l2", "random_state"} if method == "adam" else \
+            {"regularization", "alpha", "cg_steps"}
+        extra = set(fold_kwargs) - names
         if extra:
             raise TypeError(f"recommend_for_histories: unexpected arguments {sorted(extra)}")
-        args = dict(steps=20, lr=None, n_neg=None, l2=None, random_state=None)
-        args.update(fold_kwargs)
-        ptr, idx, (W, b) = self._fold_in_device(histories, return_loss=False, **args)
+        if method == "als":
+            args = dict(regularization=None, alpha=None, cg_steps=None)
+            args.update(fold_kwargs)
+            ptr, idx, (W, b) = self._fold_in_als_device(histories, **args)
+        else:
+            args = dict(steps=20, lr=None, n_neg=None, l2=None, random_state=None)
+            args.update(fold_kwargs)
+            ptr, idx, (W, b) = self._fold_in_device(histories, return_loss=False, **args)
         n = len(ptr) - 1
         ids = np.empty((n, k), dtype=np.int64)
         scores = np.empty((n, k), dtype=np.float32)
