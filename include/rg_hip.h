@@ -927,6 +927,15 @@ int rg_mf_score_users(void *stream, const float *user_w, const float *item_w,
                       const float *user_b, const float *item_b, int32_t dim,
                       int64_t num_items, const int64_t *users_dev, int64_t n_users,
                       float *out_dev, int64_t ld);
+/* The same block WITHOUT the sigmoid (rg_mf_score.hip, the same kernel with a raw epilogue):
+ *     out[r][c] = (<user_w[users[r]], item_w[c]> + user_b[users[r]]) + item_b[c],
+ * what a model whose prediction is the raw score reads (the pooling sequence model, with its
+ * representations as the user table).  Arguments, layout, determinism and refusals are
+ * rg_mf_score_users'. */
+int rg_mf_score_users_raw(void *stream, const float *user_w, const float *item_w,
+                          const float *user_b, const float *item_b, int32_t dim,
+                          int64_t num_items, const int64_t *users_dev, int64_t n_users,
+                          float *out_dev, int64_t ld);
 /* The k best items of each of those users without the score block (rg_mf_topk.hip), what
  * recommend() reads.  Row r's key for column c is
  *     -inf if c is in row r's exclusion list, else -inf if the score is NaN, else the score
@@ -970,6 +979,64 @@ int rg_mf_topk_users(void *stream, const float *user_w, const float *item_w,
                      int64_t num_items, const int64_t *users_dev, int64_t n_users,
                      const int64_t *exc_ptr, const int32_t *exc_idx, int32_t k, int32_t splits,
                      void *workspace_dev, int32_t *out_idx, float *out_scores);
+
+/* ------------------------------------------------------------------------------
+ * The pooling sequence model (rg_seq.hip): next-item prediction from the mean of the items seen
+ * so far (spotlight/sequence/representations.py PoolNet of the reference; Covington et al. 2016).
+ * Items are 1 .. num_items - 1, id 0 is padding; E [num_items][dim] and b [num_items] (device,
+ * fp32) have a zero row 0 that never receives a gradient (torch's padding_idx = 0).  For a
+ * left-padded sequence s[0 .. L):
+ *     c_t = #{j < t : s_j != 0},  S_t = sum_{j < t} E[s_j],  r_t = S_t / (c_t + 1)   (r_0 = 0),
+ * the score of item i at position t is z = b[i] + <r_t, E[i]>, and r_L serves.  Padding is
+ * counted per id; the reference counts per stored float (emb != 0.0), which differs only when a
+ * stored float is exactly 0.0.
+ *
+ * rg_seq_pool_grads: forward, loss and backward of one step in one launch (plus the one-wave loss
+ * reduction).  seq [B][L] and neg [K][B][L] are int64 ids (device); with zp[b][t] the score of
+ * seq[b][t] and zn[k][b][t] that of neg[k][b][t], both under r_t, and mask = (seq != 0), the loss
+ * is spotlight/losses.py on raw scores,
+ *   RG_LOSS_BPR             sum_{k,b,t} mask (1 - sigmoid(zp - zn_k))     * inv_count
+ *   RG_LOSS_HINGE           sum_{k,b,t} mask max(0, zn_k - zp + 1)        * inv_count
+ *   RG_LOSS_ADAPTIVE_HINGE  sum_{b,t}   mask max(0, max_k zn_k - zp + 1)  * inv_count
+ * (equal maxima go to the lowest k), inv_count = 1 / mask.sum() from the caller.  loss_out
+ * (device, 1 float) receives it; grad [num_items][dim + 1] (device, ZEROED by the caller or by
+ * rg_seq_adam_dense) receives d loss / d E[i] in columns [0, dim) and d loss / d b[i] in column
+ * dim, from the targets, from the negatives (a negative equal to 0 receives nothing) and through
+ * r_t to every item before t.  Row 0 is not written.  workspace holds
+ * rg_seq_pool_workspace_len(B, L, K) floats (-1 for unsupported arguments).
+ * A sequence is owned by one group of dim / 4 lanes (16 or 64 when dim is not 8 .. 256 by powers
+ * of two) that walks it forward with S in registers and back with the suffix sum of the
+ * per-position gradients in registers.  The gradient rows are FLOAT ATOMIC adds: their order, and
+ * so the last bits of a gradient, differ from run to run; the loss is reduced in a fixed order
+ * and is the same bits on every run.  An id outside [0, num_items) is read as padding.
+ * RG_E_ARG (rg_last_error names the reason, no HIP call made, nothing written) on a null
+ * pointer, dim not a multiple of 4 in [4, 256], num_items outside [2, INT_MAX], L outside
+ * [1, RG_SEQ_MAX_LEN], K outside [1, RG_SEQ_MAX_NEG], B < 1, a loss other than the three above
+ * (the reference's pointwise loss takes probabilities and drops the mask), or inv_count outside
+ * (0, 1].
+ *
+ * rg_seq_adam_dense: torch.optim.Adam's update (opt_update, the MF dense pass's op order; coupled
+ * weight decay; opt->step_size / bias_correction2_sqrt are the step's) of every row but row 0
+ * from grad, with the moments mE, vE [num_items][dim] and mb, vb [num_items]; grad is zeroed
+ * (row 0's slot too) for the next step.  Row 0 of the parameters and moments is not touched.
+ * RG_E_ARG on a null pointer, dim outside [1, 256], num_items outside [1, INT_MAX] or an
+ * optimizer other than Adam.
+ *
+ * rg_seq_pool_repr: out[r] = r_L of sequence r, [n][dim] (device).  ptr null: ids is a padded
+ * [n][L] block; otherwise a CSR, sequence r being ids[ptr[r] .. ptr[r + 1]) (ptr ascending,
+ * int64) and L is not read.  An empty sequence gives the zero row.  RG_E_ARG as above; n == 0:
+ * RG_OK, no launch.
+ * ---------------------------------------------------------------------------- */
+#define RG_SEQ_MAX_LEN 1024
+#define RG_SEQ_MAX_NEG 16
+int64_t rg_seq_pool_workspace_len(int64_t B, int32_t L, int32_t K);
+int rg_seq_pool_grads(void *stream, const int64_t *seq, const int64_t *neg, const float *E, const float *b,
+                      int32_t dim, int64_t num_items, int64_t B, int32_t L, int32_t K, int32_t loss,
+                      float inv_count, float *grad, float *workspace, float *loss_out);
+int rg_seq_adam_dense(void *stream, float *E, float *b, float *mE, float *vE, float *mb, float *vb,
+                      float *grad, int32_t dim, int64_t num_items, const rg_opt_t *opt);
+int rg_seq_pool_repr(void *stream, const float *E, int32_t dim, int64_t num_items, const int64_t *ids,
+                     const int64_t *ptr, int32_t L, int64_t n, float *out);
 
 /* ------------------------------------------------------------------------------
  * MF fold-in (rg_mf_fold.hip): fit the rows and biases of users that were not in the training

@@ -404,6 +404,20 @@ SIGNATURES = [
                                            ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(Opt),
                                            ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.c_void_p]),
+    ("rg_mf_score_users_raw", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p,
+                                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64]),
+    ("rg_seq_pool_workspace_len", ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
+    ("rg_seq_pool_grads", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64,
+                                         ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("rg_seq_adam_dense", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_int32, ctypes.c_int64, ctypes.POINTER(Opt)]),
+    ("rg_seq_pool_repr", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
+                                        ctypes.c_void_p]),
     ("rg_als_long_row_len", ctypes.c_int32, []),
     ("rg_als_gram_workspace_len", ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32]),
     ("rg_als_gram", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_float,

@@ -22,7 +22,7 @@ SOURCES = ["rg_api.cpp", "rg_sampler.hip", "rg_mf.hip", "rg_mf_alt.hip", "rg_ste
            "rg_comm.cpp", "rg_mtjump.cpp", "rg_ncf.hip", "rg_gemm.hip", "rg_gan.hip", "rg_eval.hip", "rg_plan.hip",
            "rg_owner.hip", "rg_uniform.hip", "rg_membw.hip", "rg_pool.cpp", "rg_ncf_score.hip",
            "rg_mf_score.hip", "rg_mf_topk.hip", "rg_item_sim.hip", "rg_topk_wide.hip", "rg_gan_score.hip",
-           "rg_mf_fold.hip", "rg_cand.hip", "rg_diverse.hip", "rg_als.hip"]
+           "rg_mf_fold.hip", "rg_cand.hip", "rg_diverse.hip", "rg_als.hip", "rg_seq.hip"]
 HEADERS = ["rg_common.h", "rg_gemm.h", "rg_mt.h", "rg_owner.h", "rg_mlp_update.h", "rg_mfma.h", "rg_mf_kernels.h",
            "rg_stepper.h", "rg_mf_score_tile.h", "rg_topk_lists.h", "rg_topk_tiles.h"]
 # the two MF translation units share rg_mf_kernels.h, which -D defines reach: always built together

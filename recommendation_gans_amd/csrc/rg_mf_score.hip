@@ -33,7 +33,7 @@ struct Args {
     float *out;
 };
 
-template <bool VEC>
+template <bool VEC, bool RAW>
 __global__ __launch_bounds__(kThreads, 2) void mf_score_kernel(Args a) {
     __shared__ __attribute__((aligned(16))) float sI[kItemFloats];
     __shared__ __attribute__((aligned(16))) float sU[kUserFloats];
@@ -41,7 +41,7 @@ __global__ __launch_bounds__(kThreads, 2) void mf_score_kernel(Args a) {
     const int64_t i0 = tile * kTile, u0 = grp * kGroup;
     v4f acc[NB];
     if (!product<VEC>(a.t, i0, u0, sI, sU, acc)) return;
-    scores(a.t, i0, u0, acc, [&](int, int64_t u, int, int64_t item, float s) { a.out[u * a.ld + item] = s; });
+    scores<RAW>(a.t, i0, u0, acc, [&](int, int64_t u, int, int64_t item, float s) { a.out[u * a.ld + item] = s; });
 }
 
 }  // namespace
@@ -49,24 +49,41 @@ __global__ __launch_bounds__(kThreads, 2) void mf_score_kernel(Args a) {
 
 using namespace rg;
 
-extern "C" int rg_mf_score_users(void *stream, const float *user_w, const float *item_w, const float *user_b,
-                                 const float *item_b, int32_t dim, int64_t num_items, const int64_t *users_dev,
-                                 int64_t n_users, float *out_dev, int64_t ld) {
+template <bool RAW>
+static int score_users(const char *name, void *stream, const float *user_w, const float *item_w, const float *user_b,
+                       const float *item_b, int32_t dim, int64_t num_items, const int64_t *users_dev,
+                       int64_t n_users, float *out_dev, int64_t ld) {
+    const std::string who(name);
     if (!user_w || !item_w || !user_b || !item_b || !users_dev || !out_dev)
-        return fail_arg("rg_mf_score_users: null pointer");
-    if (dim < 1 || dim > 256) return fail_arg("rg_mf_score_users: dim must be in [1, 256]");
-    if (num_items < 1) return fail_arg("rg_mf_score_users: num_items < 1");
-    if (ld < num_items) return fail_arg("rg_mf_score_users: ld < num_items");
-    if (n_users < 0) return fail_arg("rg_mf_score_users: n_users < 0");
+        return fail_arg(who + ": null pointer");
+    if (dim < 1 || dim > 256) return fail_arg(who + ": dim must be in [1, 256]");
+    if (num_items < 1) return fail_arg(who + ": num_items < 1");
+    if (ld < num_items) return fail_arg(who + ": ld < num_items");
+    if (n_users < 0) return fail_arg(who + ": n_users < 0");
     if (n_users == 0) return RG_OK;
     const int64_t tiles = (num_items + kTile - 1) / kTile, groups = (n_users + kGroup - 1) / kGroup;
     if (tiles > (int64_t)(UINT_MAX / kThreads) / groups)     // a launch holds fewer than 2^32 threads
-        return fail_arg("rg_mf_score_users: too many users x items for one launch (item tiles x user groups > 2^24 - 1)");
+        return fail_arg(who + ": too many users x items for one launch (item tiles x user groups > 2^24 - 1)");
     const Args a{{user_w, item_w, user_b, item_b, users_dev, num_items, n_users, dim}, ld, groups, out_dev};
     const dim3 grid((unsigned)(tiles * groups));
     if (vec_loads(user_w, item_w, dim))
-        hipLaunchKernelGGL((mf_score_kernel<true>), grid, dim3(kThreads), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL((mf_score_kernel<true, RAW>), grid, dim3(kThreads), 0, (hipStream_t)stream, a);
     else
-        hipLaunchKernelGGL((mf_score_kernel<false>), grid, dim3(kThreads), 0, (hipStream_t)stream, a);
-    return check_launch("rg_mf_score_users");
+        hipLaunchKernelGGL((mf_score_kernel<false, RAW>), grid, dim3(kThreads), 0, (hipStream_t)stream, a);
+    return check_launch(name);
+}
+
+extern "C" int rg_mf_score_users(void *stream, const float *user_w, const float *item_w, const float *user_b,
+                                 const float *item_b, int32_t dim, int64_t num_items, const int64_t *users_dev,
+                                 int64_t n_users, float *out_dev, int64_t ld) {
+    return score_users<false>("rg_mf_score_users", stream, user_w, item_w, user_b, item_b, dim, num_items, users_dev,
+                              n_users, out_dev, ld);
+}
+
+// the same block before the sigmoid
+extern "C" int rg_mf_score_users_raw(void *stream, const float *user_w, const float *item_w, const float *user_b,
+                                     const float *item_b, int32_t dim, int64_t num_items, const int64_t *users_dev,
+                                     int64_t n_users, float *out_dev, int64_t ld) {
+    return score_users<true>("rg_mf_score_users_raw", stream, user_w, item_w, user_b, item_b, dim, num_items,
+                             users_dev, n_users, out_dev, ld);
 }

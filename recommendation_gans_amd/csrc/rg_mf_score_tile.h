@@ -146,7 +146,8 @@ __device__ __forceinline__ bool product(const Tables &a, int64_t i0, int64_t u0,
 // The scores of an active wave's accumulators: sink(ul, u, nb, item, score) for every user
 // u = u0 + ul < n_users of the wave (ul = 16 wave + 4 g + r in the group) and every item
 // i0 + 16 nb + j < num_items.
-template <class Sink>
+// RAW: the score before the sigmoid (rg_mf_score_users_raw).
+template <bool RAW = false, class Sink>
 __device__ __forceinline__ void scores(const Tables &a, int64_t i0, int64_t u0, const v4f (&acc)[NB], Sink &&sink) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, j = lane & 15;
     float bi[NB];
@@ -164,7 +165,10 @@ __device__ __forceinline__ void scores(const Tables &a, int64_t i0, int64_t u0, 
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) {
             const int64_t item = i0 + 16 * nb + j;
-            if (item < a.num_items) sink(ul, u, nb, item, sigmoidf_ref((acc[nb][r] + bu) + bi[nb]));
+            if (item < a.num_items) {
+                const float z = (acc[nb][r] + bu) + bi[nb];
+                sink(ul, u, nb, item, RAW ? z : sigmoidf_ref(z));
+            }
         }
     }
 }

@@ -151,6 +151,16 @@ most ``block_elems`` padded elements; ``torch_reps`` repetitions).  Device event
 largest difference of the two results, and the kernel's distance from its two bounds:
 (cg_steps + 1) nnz d 4 gathered bytes at 8 TB/s, and its flops at the fp32 vector peak.  One JSON
 line per d.
+
+    python -m recommendation_gans_amd.eval_time --metric seq_pool [--items 26744] [--reps 20]
+
+times the pooling sequence model (``seq_engine.py``: rg_seq_pool_grads + rg_seq_adam_dense, and one
+``recommend_next`` block of 4096 sequences) against the chain of torch ops each replaces -- the
+float32 formulas of ``seq_engine.pool_loss_torch`` with autograd and a hand-written dense Adam, and
+gather / cumsum / GEMM / topk -- on the same GPU in the same process, the two alternating: training
+steps at B in {256, 4096}, L in {10, 50}, d in {32, 64, 128}, bpr.  Device events, min / median, the
+largest difference of the two results, and the step's distance from max(gathered bytes at 8 TB/s,
+flops at the fp32 vector peak).  One JSON line per shape.
 """
 import argparse
 import contextlib
@@ -1148,6 +1158,106 @@ def main_gan_score(args):
     return out
 
 
+def main_seq_pool(args):
+    """``--metric seq_pool``: one training step (rg_seq_pool_grads + rg_seq_adam_dense) and one
+    recommend_next block against the torch ops they replace.  ``bound_ms`` of a step: the forward
+    walk gathers 2 rows per position, the reverse walk 2 more, 4 B L (d + 1) floats; the dense Adam
+    pass streams 7 floats per parameter (gradient read and zeroed, p, m, v read and written); flops:
+    about 8 d per position."""
+    from . import seq_engine
+    from .spotlight.sequence import ImplicitSequenceModel
+    dev = torch.device("cuda:0")
+    I, lr = args.items, 1e-2
+    out = []
+    for d in (32, 64, 128):
+        g = torch.Generator().manual_seed(d)
+        E0 = torch.randn(I, d, generator=g) / d
+        E0[0] = 0
+        for B in (256, 4096):
+            for L in (10, 50):
+                rs = np.random.RandomState(B + L + d)
+                seq = torch.from_numpy(rs.randint(1, I, (B, L))).to(dev)
+                seq[: B // 4, : L // 2] = 0
+                neg = torch.from_numpy(rs.randint(0, I, (1, B, L))).to(dev)
+                count = int((seq != 0).sum())
+                E, b = E0.to(dev).clone(), torch.zeros(I, device=dev)
+                mom = [torch.zeros_like(E), torch.zeros_like(E), torch.zeros_like(b), torch.zeros_like(b)]
+                grad = torch.zeros(I, d + 1, device=dev)
+                Et, bt = E.clone().requires_grad_(True), b.clone().requires_grad_(True)
+                opt = torch.optim.Adam([Et, bt], lr=lr)
+
+                def new():
+                    lv, _ = seq_engine.pool_grads(E, b, seq, neg, "bpr", grad=grad, mask_count=count, checked=True)
+                    seq_engine.adam_dense(E, b, *mom, grad, 1, lr)
+                    return lv
+
+                def old():
+                    opt.zero_grad(set_to_none=True)
+                    lv = seq_engine.pool_loss_torch(Et, bt, seq, neg, "bpr")
+                    lv.backward()
+                    with torch.no_grad():
+                        Et.grad[0] = 0
+                        bt.grad[0] = 0
+                    opt.step()
+                    return lv.detach()
+
+                lv_new, g_new = seq_engine.pool_grads(E, b, seq, neg, "bpr", mask_count=count, checked=True)
+                lv_old = seq_engine.pool_loss_torch(Et, bt, seq, neg, "bpr")
+                gE, gb = torch.autograd.grad(lv_old, [Et, bt])
+                gE[0] = 0
+                gb[0] = 0
+                diff = float(max((g_new[:, :d] - gE).abs().max(), (g_new[:, d] - gb).abs().max()))
+                loss_diff = abs(float(lv_new) - float(lv_old))
+                for _ in range(3):
+                    new(), old()
+                t_new, t_old = [], []
+                for _ in range(args.reps):
+                    t_new += timed(new, 1)
+                    t_old += timed(old, 1)
+                bound = max((4.0 * count * (d + 1) * 4 + 7.0 * I * (d + 1) * 4) / PEAK_HBM,
+                            8.0 * d * count / PEAK_FP32_MFMA) * 1e3
+                r = {"metric": "seq_pool", "workload": "train_step", "dim": d, "B": B, "L": L, "items": I, "loss": "bpr",
+                     "reps": args.reps, "kernel_ms": stats(t_new), "torch_ms": stats(t_old),
+                     "median_ratio_torch_over_kernel": float(np.median(t_old) / np.median(t_new)),
+                     "max_abs_grad_diff": diff, "abs_loss_diff": loss_diff, "bound_ms": bound,
+                     "kernel_over_bound": float(np.median(t_new) / bound)}
+                print(json.dumps(r), flush=True)
+                out.append(r)
+                del opt, Et, bt, E, b, mom, grad
+        # serving: one recommend_next block of 4096 sequences of 50 items, k = 10
+        model = ImplicitSequenceModel(embedding_dim=d)
+        model.set_tables(E0, torch.zeros(I), device=dev)
+        rs = np.random.RandomState(d)
+        seqs = rs.randint(1, I, (4096, 50))
+        seq_dev = torch.from_numpy(seqs).to(dev)
+
+        def new_rec():
+            return model.recommend_next(seqs, 10)
+
+        def old_rec():
+            _, rL = seq_engine.pool_reprs_torch(model.item_embeddings, seq_dev)
+            blk = rL @ model.item_embeddings.T + model.item_biases[None, :]
+            blk[:, 0] = float("-inf")
+            blk.scatter_(1, seq_dev, float("-inf"))
+            return torch.topk(blk, 10, dim=1).indices.cpu().numpy()
+
+        for _ in range(2):
+            a, c = new_rec(), old_rec()
+        t_new, t_old = [], []
+        for _ in range(args.reps):
+            t_new += timed(new_rec, 1)
+            t_old += timed(old_rec, 1)
+        r = {"metric": "seq_pool", "workload": "recommend_next", "dim": d, "sequences": 4096, "L": 50, "items": I,
+             "k": 10, "reps": args.reps, "kernel_ms": stats(t_new), "torch_ms": stats(t_old),
+             "median_ratio_torch_over_kernel": float(np.median(t_old) / np.median(t_new)),
+             "rows_with_other_ids": int((a != c).any(axis=1).sum())}
+        print(json.dumps(r), flush=True)
+        out.append(r)
+        del model
+        torch.cuda.empty_cache()
+    return out
+
+
 def main_scores(args):
     """The default mode: one block of ``--users`` users against every item, NCFEngine.score_users
     (rg_ncf_score_users) against the pairwise NCFEngine.scores_torch."""
@@ -1197,7 +1307,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--metric", choices=("scores", "mrr", "slates", "pairs", "mf_scores", "mf_topk", "item_sim",
                                         "gan_recommend", "topk_wide", "gan_score", "fold_in", "candidates", "mmr",
-                                        "als"),
+                                        "als", "seq_pool"),
                     default="scores")
     ap.add_argument("--batch", type=int, default=8192)
     ap.add_argument("--users", type=int, default=None)
@@ -1217,7 +1327,7 @@ def main(argv=None):
             "mf_scores": main_mf_scores, "mf_topk": main_mf_topk, "item_sim": main_item_sim,
             "gan_recommend": main_gan_recommend, "topk_wide": main_topk_wide,
             "gan_score": main_gan_score, "fold_in": main_fold_in, "candidates": main_candidates,
-            "mmr": main_mmr, "als": main_als}[args.metric](args)
+            "mmr": main_mmr, "als": main_als, "seq_pool": main_seq_pool}[args.metric](args)
 
 
 if __name__ == "__main__":

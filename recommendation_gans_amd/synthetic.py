@@ -88,3 +88,35 @@ def movielens_like(shape=ML20M, seed=0, zipf_s=1.0, pool_seed=None):
     pool_i = prs.randint(0, I, len(tu)).astype(np.int64)
     pop = np.bincount(i, minlength=I).astype(np.int64)
     return SyntheticSplit(U, I, tu, ti, vu, vi, su, si, pool_u, pool_i, pop)
+
+
+def generate_sequential(num_users=100, num_items=1000, num_interactions=10000, concentration=0.1, order=3,
+                        random_state=None):
+    """Interactions whose order matters, for the sequence model's tests and timing: one chain of
+    ``num_interactions`` items in 1 .. num_items - 1 (0 is the padding id) drawn from a Markov
+    chain of the given ``order`` and dealt to users in sorted blocks, timestamps ascending.
+
+    Every item has a row of transition probabilities drawn from Dirichlet(concentration): the
+    closer to zero, the fewer successors an item has and the more predictable the chain.  With
+    ``order`` > 1 the next item's distribution is the mean of the rows of the last ``order``
+    items."""
+    from .spotlight.interactions import Interactions
+    rs = random_state if random_state is not None else np.random.RandomState()
+    states = num_items - 1
+    if states < 1 or order < 1:
+        raise ValueError("generate_sequential needs num_items >= 2 and order >= 1")
+    rows = rs.dirichlet(np.full(states, float(concentration)), states)
+    cum = np.cumsum(rows, axis=1)
+    cum /= cum[:, -1:]
+    chain = np.empty(num_interactions, dtype=np.int64)
+    chain[:order] = rs.randint(0, states, min(order, num_interactions))
+    draws = rs.random_sample(num_interactions)
+    picks = rs.randint(0, order, num_interactions)
+    for t in range(order, num_interactions):
+        # the mean of `order` rows, sampled as: pick one of the last `order` items, then its row
+        src = chain[t - 1 - picks[t]]
+        chain[t] = min(int(np.searchsorted(cum[src], draws[t], side="right")), states - 1)
+    user_ids = np.sort(rs.randint(0, num_users, num_interactions)).astype(np.int32)
+    return Interactions(user_ids, (chain + 1).astype(np.int32), ratings=np.ones(num_interactions, np.float32),
+                        timestamps=np.arange(num_interactions, dtype=np.int32), num_users=num_users,
+                        num_items=num_items)
