@@ -4,13 +4,21 @@ objective in include/rg_hip.h (rg_mf_fold_in_users) with hand-written gradients,
 reference in float64 and, run in float32 with three summation orders, measures the error a float32
 evaluation of the same formulas has (``E32``).
 
-The cases cover dim {1, 3, 16, 64, 65, 256}, users {1, 5, 130}, history lengths {0, 1, 2, 63, 64,
-65, 200} mixed in one call, n_neg {0, 1, 3, 5} (5 is past the kernel's chunk of 4 negatives, the
-odd lengths past its block of 2 positives), steps {1, 2, 8}, the four losses, weight decay {0,
-1e-3} and zero / random starts -- a covering list, not the product.  Chosen before any GPU run by
-one rule: every case compares at least ~250 elements (a few users go with a large dim, dim 1 and 3
-with 130 users), because E32 and the kernel's deviation are both maxima over the case's elements
-and the maximum over a dozen elements is mostly chance.
+The cases cover every row layout the kernel is instantiated for (rg_common.h dispatch_dim; LPU
+lanes x EPL elements per lane), by dim:
+    8 / 16 / 32 / 64 / 128 / 256   the 16-byte layouts of 2 / 4 / 8 / 16 / 32 / 64 lanes x 4
+    1, 3                           scalar, 16 lanes x 1        24         scalar, 16 lanes x 2
+    48                             scalar, 16 lanes x 4        65, 96     scalar, 64 lanes x 2
+    160                            scalar, 64 lanes x 3        200        scalar, 64 lanes x 4
+with users {1, 5, 130}, history lengths {0, 1, 2, 63, 64, 65, 200} mixed in one call, n_neg {0, 1,
+3, 5} (5 is past the kernel's chunk of 4 negatives, the odd lengths past its block of 2 positives),
+steps {1, 2, 8}, the four losses, weight decay {0, 1e-3} and zero / random starts -- a covering
+list, not the product.  Chosen before any GPU run by one rule: every case compares at least ~250
+elements (a few users go with a large dim, the dims up to 48 with 130 users), because E32 and the
+kernel's deviation are both maxima over the case's elements and the maximum over a dozen elements
+is mostly chance.  ``UNALIGNED`` names the cases the tests run again on tables that start 4 bytes
+off a 16-byte boundary, where every dim takes a scalar layout: the power-of-two dims then fill
+every lane slot exactly (dim == LPU * EPL), and dim 24 keeps its layout.
 """
 import functools
 
@@ -42,8 +50,19 @@ CASES = [
     (1, 130, 5, 8, "adaptive_hinge", 0.0, "random"),
     (16, 130, 1, 2, "hinge", 0.0, "zero"),
     (3, 130, 0, 2, "pointwise", 0.0, "zero"),
+    # the layouts the list above never selected (every one admitted as first written)
+    (8, 130, 5, 8, "bpr", 1e-3, "random"),
+    (32, 130, 3, 2, "adaptive_hinge", 0.0, "zero"),
+    (24, 130, 1, 8, "pointwise", 0.0, "random"),
+    (48, 130, 5, 1, "hinge", 1e-3, "zero"),
+    (128, 5, 3, 8, "bpr", 0.0, "zero"),
+    (160, 5, 1, 2, "adaptive_hinge", 1e-3, "random"),
+    (200, 5, 5, 8, "hinge", 0.0, "random"),
+    (96, 5, 3, 2, "pointwise", 1e-3, "random"),
 ]
 CASE_IDS = ["d%d-u%d-n%d-t%d-%s-wd%g-%s" % c for c in CASES]
+# the cases run again on unaligned tables: the first case of dims 8, 16, 64, 128 and 24
+UNALIGNED = [next(i for i, c in enumerate(CASES) if c[0] == dim) for dim in (8, 16, 64, 128, 24)]
 
 
 def history_lengths(users):

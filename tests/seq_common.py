@@ -10,12 +10,21 @@ difference below ``fold_in_common.CANCEL`` of an element's sum of |terms| is rou
 |terms| is exact: the gradient is a sum of products dz * (element of E) * 1 / (c + 1) with
 non-negative coefficients, so the same graph evaluated at |dz|, |E| sums their magnitudes.
 
-Cases are a covering list chosen before any GPU run: d {4, 8, 64, 128, 256} (scalar 16-lane, the
-vector layouts of 2, 16, 32 and 64 lanes) plus 12, 16 and 200 (the other scalar layouts, 4 lanes),
-L {1, 2, 5, 33}, B {1, 3, 257}, K {1, 5}, 7 items (every row collides in the atomics) and 1000,
-the three losses.  A hinge whose argument, or an adaptive hinge whose two highest negatives (of
-different items), come within ``fold_in_common.TIE`` of a kink in float64 would make the gradient
-a coin toss in float32; ``kink_margin`` measures it and test_seq_cpu.py checks that no case has one.
+Cases are a covering list chosen before any GPU run.  They select every row layout the kernel is
+instantiated for (rg_common.h dispatch_dim; LPU lanes x EPL elements per lane), by d:
+    8 / 16 / 32 / 64 / 128 / 256   the 16-byte layouts of 2 / 4 / 8 / 16 / 32 / 64 lanes x 4
+    4, 12                          scalar, 16 lanes x 1        24     scalar, 16 lanes x 2
+    48                             scalar, 16 lanes x 4        96     scalar, 64 lanes x 2
+    160                            scalar, 64 lanes x 3        200    scalar, 64 lanes x 4
+with L {1, 2, 5, 33}, B {1, 3, 257}, K {1, 5}, 7 items (every row collides in the atomics) and
+1000, the three losses.  A hinge whose argument, or an adaptive hinge whose two highest negatives
+(of different items), come within ``fold_in_common.TIE`` of a kink in float64 would make the
+gradient a coin toss in float32; ``kink_margin`` measures it and test_seq_cpu.py checks that no
+case has one -- the edge cases below (``EDGE_CASES``: padding anywhere, ids outside the table, rows
+of padding alone, the longest sequence with the most negatives) included.  ``UNALIGNED`` names the
+cases the tests run again on a table that starts 4 bytes off a 16-byte boundary, where every d
+takes a scalar layout: the power-of-two dims then fill every lane slot exactly (d == LPU * EPL),
+and d 24 keeps its layout.
 """
 import functools
 import os
@@ -46,8 +55,23 @@ CASES = [
     (200, 2, 3, 1, 1000, "hinge"),
     (256, 5, 3, 5, 1000, "adaptive_hinge"),
     (256, 33, 257, 1, 7, "bpr"),
+    # the layouts the list above never selected (every one admitted as first written)
+    (32, 33, 257, 5, 7, "hinge"),
+    (24, 5, 3, 5, 1000, "adaptive_hinge"),
+    (48, 33, 257, 1, 1000, "bpr"),
+    (96, 2, 3, 5, 7, "hinge"),
+    (160, 5, 257, 1, 7, "adaptive_hinge"),
 ]
 CASE_IDS = ["d%d-L%d-B%d-K%d-I%d-%s" % c for c in CASES]
+# the cases run again on an unaligned table: of dims 8, 16, 64, 128 and 24 the case with the most
+# (position, negative) pairs L * B * K, the first of equals
+UNALIGNED = [max((i for i, c in enumerate(CASES) if c[0] == dim), key=lambda i: (np.prod(CASES[i][1:4]), -i))
+             for dim in (8, 16, 64, 128, 24)]
+
+
+def outside_ids(num_items):
+    """The out-of-range ids the kernels must read as padding (include/rg_hip.h)."""
+    return np.array([num_items, num_items + 5, -1, 2 ** 40], dtype=np.int64)
 
 
 def make_tables(num_items, d, rs, scale=0.7):
@@ -168,12 +192,79 @@ def case_data(i):
     """Case i, computed once per process and shared (read-only): the float64 reference with the
     sums of |terms|, and E32, the largest deviation of the float32 CPU evaluation from it."""
     d, L, B, K, num_items, loss = CASES[i]
-    case = make_case(d, L, B, K, num_items)
+    return data_of(make_case(d, L, B, K, num_items), loss)
+
+
+def data_of(case, loss):
+    """What ``case_data`` holds, of any case."""
     r64 = grads(case, loss, torch.float64, abs_terms=True)
     r32 = grads(case, loss, torch.float32)
     e32 = max(float(np.abs(r32["gE"].astype(np.float64) - r64["gE"]).max()),
               float(np.abs(r32["gb"].astype(np.float64) - r64["gb"]).max()))
     return dict(case=case, loss=loss, r64=r64, r32=r32, e32=e32)
+
+
+# ------------------------------------------------------------------ the entries' edges
+def scatter_case(d, B=67, L=33, K=5, num_items=40):
+    """Padding anywhere: about a third of the positions of left-padded sequences zeroed at random,
+    row 0 ending in a zero, every row keeping at least one item.  67 rows are more than one wave of
+    every layout."""
+    case = make_case(d, L, B, K, num_items, seed=1)
+    rs = np.random.RandomState(977 + d)
+    seq = case["seq"]
+    seq[rs.random_sample(seq.shape) < 0.3] = 0
+    seq[0, -1] = 0
+    for r in np.flatnonzero((seq != 0).sum(1) == 0):
+        seq[r, L // 2] = 1 + r % (num_items - 1)
+    return case
+
+
+def outside_pair(case):
+    """(outside, inside): ``case`` with its padding zeros in seq, and a tenth of neg, replaced by ids
+    outside [0, num_items), and the same case with zeros in those places."""
+    rs = np.random.RandomState(31)
+    bad = outside_ids(case["num_items"])
+    pad = case["seq"] == 0
+    hit = rs.random_sample(case["neg"].shape) < 0.1
+    out = dict(case, seq=case["seq"].copy(), neg=case["neg"].copy())
+    ins = dict(case, seq=case["seq"].copy(), neg=case["neg"].copy())
+    out["seq"][pad] = bad[np.arange(pad.sum()) % len(bad)]
+    out["neg"][hit] = bad[np.arange(hit.sum()) % len(bad)]
+    ins["neg"][hit] = 0
+    return out, ins
+
+
+def empty_rows_case(d, B=9, L=5, K=3, num_items=40):
+    """Rows 4 and 8 (the last) are padding alone; the others are ``scatter_case``'s."""
+    case = scatter_case(d, B, L, K, num_items)
+    case["seq"][[4, 8]] = 0
+    return case
+
+
+def max_len_case():
+    """RG_SEQ_MAX_LEN positions with RG_SEQ_MAX_NEG negatives: row 0 full, row 1 half padding,
+    row 2 a single item."""
+    return make_case(8, 1024, 3, 16, 50)
+
+
+# (name, d, loss): every edge case whose gradients meet the float64 oracle
+EDGE_CASES = [("scatter", 8, "bpr"), ("scatter", 8, "hinge"), ("scatter", 64, "bpr"), ("scatter", 64, "hinge"),
+              ("inside", 8, "hinge"), ("inside", 64, "bpr"), ("empty", 8, "adaptive_hinge"), ("maxlen", 8, "bpr")]
+
+
+@functools.lru_cache(maxsize=None)
+def edge_case(name, d):
+    if name == "scatter":
+        return scatter_case(d)
+    if name in ("inside", "outside"):
+        return outside_pair(scatter_case(d))[name == "inside"]
+    return empty_rows_case(d) if name == "empty" else max_len_case()
+
+
+@functools.lru_cache(maxsize=None)
+def edge_data(name, d, loss):
+    """``data_of`` of an edge case, computed once per process (read-only)."""
+    return data_of(edge_case(name, d), loss)
 
 
 def gradient_excess(gE, gb, data):

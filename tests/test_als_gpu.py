@@ -1,8 +1,11 @@
 """rg_als_gram and rg_als_solve_rows on the GPU: parity with the float64 numpy restatement inside
 twice the error of a float32 evaluation of the same formulas (E32, tests/als_common.py), bit
 invariance of a row against its place in the call on both sides of the kernel's path threshold, the
-Gram matrix, cg_steps = 0, guard elements, and ``fit_als`` / ``fold_in_users_als`` /
-``recommend_for_histories(method=)`` end to end.  300 items; every case in a few seconds.
+same parity on tables that start off a 16-byte boundary (the entry's scalar-layout dispatch), calls
+large enough that a workgroup of either kernel takes a second trip over the rows (sized from the
+device's compute-unit count), the Gram matrix, cg_steps = 0, guard elements, and ``fit_als`` /
+``fold_in_users_als`` / ``recommend_for_histories(method=)`` end to end.  300 items; every case in a
+few seconds.
 
 The parity bound is measured, not picked: E32 is the largest deviation from float64 of the float32
 restatement with the lists summed forward, reversed and pairwise; the kernel -- one more ordering of
@@ -62,6 +65,147 @@ def test_parity_with_the_float64_restatement_within_twice_the_float32_error(i):
     assert np.isfinite(x).all() and np.isfinite(lv).all()
     assert dev <= 2 * d["e32"]
     assert dev_loss <= 2 * d["e32_loss"]
+
+
+def _view(host, off):
+    """``host`` as a contiguous device view ``off`` floats into a buffer of -7 (guards on both sides)."""
+    host = np.ascontiguousarray(host)
+    buf = torch.full((off + host.size + GUARD,), -7.0, dtype=torch.float32, device=DEV)
+    view = buf[off:off + host.size].view(host.shape)
+    view.copy_(t(host))
+    assert view.is_contiguous() and view.data_ptr() % 16 == 4 * off
+    return buf, view
+
+
+def run_views(case, cg, off_other, off_x):
+    """The kernel with other_table / x_inout ``off_other`` / ``off_x`` floats into larger buffers
+    (``solve_rows`` hands contiguous views through as they are): host (x, loss)."""
+    ybuf, Y = _view(case["Y"], off_other)
+    xbuf, x = _view(case["X0"], off_x)
+    _, lv = als.solve_rows(Y, t(case["G"]).to(DEV), t(case["ptr"]), t(case["idx"]),
+                           None if case["val"] is None else t(case["val"]), case["alpha"], cg, x, return_loss=True)
+    torch.cuda.synchronize()
+    yb, xb = ybuf.cpu().numpy(), xbuf.cpu().numpy()
+    assert yb[off_other:off_other + Y.numel()].tobytes() == case["Y"].tobytes(), "other_table written"
+    for buf, off, size in ((yb, off_other, Y.numel()), (xb, off_x, x.numel())):
+        assert (buf[:off] == -7.0).all() and (buf[off + size:] == -7.0).all(), "elements outside a table written"
+    return x.cpu().numpy(), lv.cpu().numpy()
+
+
+@pytest.mark.parametrize("which", ["other_table and x_inout", "x_inout alone"])
+@pytest.mark.parametrize("i", ac.UNALIGNED, ids=[ac.CASE_IDS[i] for i in ac.UNALIGNED])
+def test_tables_off_a_16_byte_boundary_meet_the_float64_restatement(i, which):
+    """The unaligned dispatch (dispatch_als's scalar layouts), held to float64 by the parity test's
+    own rule; at dim 24 the aligned call selects the same layout, so the bits are the aligned call's."""
+    d = ac.case_data(i)
+    assert d["admitted"], (d["e32"], d["xmax"])
+    case = d["case"]
+    x, lv = run_views(case, d["cg"], 1 if which == "other_table and x_inout" else 0, 1)
+    dev = float(np.abs(x.astype(np.float64) - d["r64"][0]).max())
+    dev_loss = float(np.abs(lv.astype(np.float64) - d["r64"][1]).max())
+    print(f"\nunaligned {which}, case {ac.CASE_IDS[i]}: kernel {dev:.3e} E32 {d['e32']:.3e} ratio {dev / d['e32']:.2f} | "
+          f"loss kernel {dev_loss:.3e} E32 {d['e32_loss']:.3e} ratio {dev_loss / d['e32_loss']:.2f}")
+    empty = np.diff(case["ptr"]) == 0
+    assert not x[empty].any() and not lv[empty].any()
+    assert np.isfinite(x).all() and np.isfinite(lv).all()
+    assert dev <= 2 * d["e32"]
+    assert dev_loss <= 2 * d["e32_loss"]
+    if case["dim"] == 24:
+        x0, lv0 = run_views(case, d["cg"], 0, 0)
+        assert x.tobytes() == x0.tobytes() and lv.tobytes() == lv0.tobytes()
+
+
+class _Resident:
+    """A case's arrays on the device once, for many calls of the entry itself on subsets of its rows."""
+
+    def __init__(self, case):
+        self.case, self.n, self.dim = case, case["rows"], case["dim"]
+        self.Y, self.G = t(case["Y"]).to(DEV), t(case["G"]).to(DEV)
+        self.ptr, self.idx = t(case["ptr"]).to(DEV), t(case["idx"]).to(DEV)
+        self.val = None if case["val"] is None else t(case["val"]).to(DEV)
+
+    def solve(self, cg, calls):
+        """x and the loss (host) after one call per entry of ``calls`` (None: every row; else the
+        row ids of that call) on a fresh copy of the start; guard elements follow both."""
+        n, dim, p = self.n, self.dim, _lib.ptr
+        xbuf = torch.full((n * dim + GUARD,), -7.0, dtype=torch.float32, device=DEV)
+        lbuf = torch.full((n + GUARD,), -7.0, dtype=torch.float32, device=DEV)
+        xbuf[:n * dim].copy_(t(self.case["X0"]).reshape(-1))
+        lib, stream = _lib.load(), _lib.stream_handle()
+        held = []                                     # the row ids stay allocated until the last call has run
+        for rows in calls:
+            rows_d = None if rows is None else t(np.ascontiguousarray(rows, np.int64)).to(DEV)
+            held.append(rows_d)
+            rc = lib.rg_als_solve_rows(stream, p(self.Y), p(self.G), dim, p(self.ptr), p(self.idx), p(self.val),
+                                       float(self.case["alpha"]), p(rows_d), n if rows is None else len(rows), cg,
+                                       p(xbuf), p(lbuf))
+            assert rc == 0, lib.rg_last_error()
+        torch.cuda.synchronize()
+        x, lv = xbuf.cpu().numpy(), lbuf.cpu().numpy()
+        assert (x[n * dim:] == -7.0).all() and (lv[n:] == -7.0).all(), "elements past x_inout or loss_out written"
+        return x[:n * dim].reshape(n, dim), lv[:n]
+
+
+def _second_trip_check(case, cg, sample, what):
+    """One call on all rows against calls of at most 130 rows each (the regime the parity cases hold
+    to float64; a row's bits do not depend on its call), and ``sample`` against the restatement."""
+    res = _Resident(case)
+    n = case["rows"]
+    x, lv = res.solve(cg, [None])
+    xs, ls = res.solve(cg, [np.arange(s, min(s + 130, n)) for s in range(0, n, 130)])
+    assert x.tobytes() == xs.tobytes() and lv.tobytes() == ls.tobytes()
+    d = ac.measure(ac.sub_case(case, sample), cg)
+    assert d["admitted"], (d["e32"], d["xmax"])
+    dev = float(np.abs(x[sample].astype(np.float64) - d["r64"][0]).max())
+    dev_loss = float(np.abs(lv[sample].astype(np.float64) - d["r64"][1]).max())
+    print(f"\n{what}: kernel {dev:.3e} E32 {d['e32']:.3e} ratio {dev / d['e32']:.2f} | "
+          f"loss kernel {dev_loss:.3e} E32 {d['e32_loss']:.3e} ratio {dev_loss / d['e32_loss']:.2f}")
+    assert dev <= 2 * d["e32"]
+    assert dev_loss <= 2 * d["e32_loss"]
+
+
+@pytest.mark.parametrize("dim", [16, 128])
+def test_short_rows_beyond_one_trip_of_the_grid_keep_their_bits(dim):
+    """als_short_kernel's workgroups stride over the tiles: its grid is capped (als_common.
+    short_grid_cap), every workgroup solves 8 tiles per trip (one per wave) and a tile is 64 / LPU
+    rows, so a call of more than cap * 8 * tile rows sends workgroups on a second trip with the staged
+    G and their p slots reused.  An eighth of them here, and the last tile is partial."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    cap, tile = ac.short_grid_cap(dim, cus)
+    one_trip = cap * ac.WAVES * tile
+    n = one_trip + one_trip // 8 + 5
+    assert n > one_trip and -(-n // tile) > cap * ac.WAVES
+    lens = np.random.RandomState(dim).randint(0, 6, n)
+    case = ac.make_case(dim, n, 0.1, 40.0, True, "random", lens=lens)
+    mid = n // 2
+    sample = np.r_[0:86, mid:mid + 85, n - 85:n]
+    assert len(sample) == 256
+    _second_trip_check(case, 3, sample, f"short rows dim {dim}: {n} rows, one trip holds {one_trip}, sample of 256")
+
+
+@pytest.mark.parametrize("dim", [16, 128])
+def test_long_rows_beyond_one_trip_of_the_grid_keep_their_bits(dim):
+    """als_long_kernel's workgroups stride over the call's rows and skip the short ones: its grid is
+    min(rows, m * CUs) with m in 1 .. 4 by the LDS of the layout (als_common.long_grid_cap).  Rows j
+    and j + 12 CUs fall to the same workgroup whatever m is (12 is a multiple of each), with 12 CUs
+    / (m CUs) - 1 skipped short rows between its two solves; the pair's lists differ in length, so
+    the reduction scratch of the first solve is overwritten by a different chunking."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    grid = ac.long_grid_cap(dim, cus)
+    firsts = [0, 1, 2, cus // 2, cus - 1, cus + 3]
+    n = 12 * cus + max(firsts) + 1 + 7
+    assert n > 4 * cus >= grid and all((j + 12 * cus) % (m * cus) == j % (m * cus) for j in firsts for m in (1, 2, 3, 4))
+    lens = np.random.RandomState(dim + 1).randint(0, 2, n)
+    T = ac.T
+    pairs = [(T, T + 1), (T + 1, 3 * T + 5), (3 * T + 5, T), (T, 3 * T + 5), (T + 1, T), (3 * T + 5, T + 1)]
+    long_rows = []
+    for j, (a, b) in zip(firsts, pairs):
+        lens[j], lens[j + 12 * cus] = a, b
+        long_rows += [j, j + 12 * cus]
+    assert len(long_rows) == 12 and (lens >= T).sum() == 12
+    case = ac.make_case(dim, n, 0.1, 40.0, True, "random", True, lens=lens)
+    sample = np.array(sorted(long_rows) + [r for r in range(3, 200) if r not in long_rows][:116])
+    _second_trip_check(case, 3, sample, f"long rows dim {dim}: {n} rows on a grid of {grid}, 12 long rows and 116 others")
 
 
 def test_loss_out_has_its_own_guard_and_is_optional():

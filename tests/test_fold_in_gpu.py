@@ -1,6 +1,7 @@
 """rg_mf_fold_in_users on the GPU: parity with the float64 reference inside twice the error of a
 float32 evaluation of the same formulas (E32, tests/fold_in_common.py), bit invariance of a user's
-result against its place in the call, the identity cases, descent, the model-level calls, and the
+result against its place in the call, the same parity on tables that start off a 16-byte boundary
+(the entry's scalar-layout dispatch), the identity cases, descent, the model-level calls, and the
 entry's refusals.  300 items; every case in a few seconds.
 
 The parity bound is measured, not picked: the numpy restatement runs in float32 with the positives
@@ -62,6 +63,72 @@ def test_parity_with_the_float64_reference_within_twice_the_float32_error(i):
     assert np.isfinite(W).all() and np.isfinite(b).all() and np.isfinite(lv).all()
     assert dev <= 2 * d["e32"]
     assert dev_loss <= 2 * d["e32_loss"]
+
+
+GUARD = 64
+
+
+def _view(host, off):
+    """``host`` as a contiguous device view ``off`` floats into a buffer of -7 (guards on both
+    sides): returns (buffer, view)."""
+    host = np.ascontiguousarray(host)
+    buf = torch.full((off + host.size + GUARD,), -7.0, dtype=torch.float32, device=DEV)
+    view = buf[off:off + host.size].view(host.shape)
+    view.copy_(torch.from_numpy(host))
+    assert view.is_contiguous() and view.data_ptr() % 16 == 4 * off
+    return buf, view
+
+
+def run_entry(case, loss, steps, wd, off_items, off_users):
+    """rg_mf_fold_in_users itself (the Python call copies the start into a fresh tensor) with
+    item_w / user_w ``off_items`` / ``off_users`` floats into larger buffers: host (W, b, loss)."""
+    n, dim, k = case["users"], case["dim"], case["n_neg"]
+    t = torch.from_numpy
+    qbuf, Q = _view(case["Q"], off_items)
+    wbuf, W = _view(case["W0"], off_users)
+    c, b = t(case["c"]).to(DEV), t(case["b0"]).to(DEV)
+    ptr, idx = t(case["ptr"]).to(DEV), t(case["idx"]).to(DEV)
+    neg = t(case["neg"]).to(DEV) if k else None
+    lv = torch.zeros(n, dtype=torch.float32, device=DEV)
+    coef = t(mf_engine.adam_step_coef(steps, fc.LR, fc.BETAS).astype(np.float32)).to(DEV)
+    o = _lib.Opt()
+    o.kind = mf_engine.OPT_KINDS["adam"]
+    o.lr, o.beta1, o.beta2, o.eps, o.weight_decay = fc.LR, fc.BETAS[0], fc.BETAS[1], fc.EPS, wd
+    o.one_minus_beta1, o.one_minus_beta2 = 1 - fc.BETAS[0], 1 - fc.BETAS[1]
+    p = _lib.ptr
+    rc = _lib.load().rg_mf_fold_in_users(_lib.stream_handle(), p(Q), p(c), dim, fc.NUM_ITEMS, p(ptr), p(idx), p(neg), k,
+                                         n, mf_engine.LOSS_KINDS[loss], ctypes.byref(o), p(coef), steps, p(W), p(b),
+                                         p(lv))
+    assert rc == 0, _lib.load().rg_last_error()
+    torch.cuda.synchronize()
+    q, w = qbuf.cpu().numpy(), wbuf.cpu().numpy()
+    assert q[off_items:off_items + Q.numel()].tobytes() == case["Q"].tobytes(), "item_w written"
+    for buf, off, size in ((q, off_items, Q.numel()), (w, off_users, W.numel())):
+        assert (buf[:off] == -7.0).all() and (buf[off + size:] == -7.0).all(), "elements outside a table written"
+    return W.cpu().numpy(), b.cpu().numpy(), lv.cpu().numpy()
+
+
+@pytest.mark.parametrize("which", ["item_w and user_w", "user_w alone"])
+@pytest.mark.parametrize("i", fc.UNALIGNED, ids=[fc.CASE_IDS[i] for i in fc.UNALIGNED])
+def test_tables_off_a_16_byte_boundary_meet_the_float64_reference(i, which):
+    """The unaligned dispatch (dispatch_fold's scalar layouts), held to float64 by the parity test's
+    own rule; at dim 24 the aligned call selects the same layout, so the bits are the aligned call's."""
+    d = fc.case_data(i)
+    case = d["case"]
+    W, b, lv = run_entry(case, d["loss"], d["steps"], d["wd"], 1 if which == "item_w and user_w" else 0, 1)
+    dev = fc.deviation(W, b, d["ref"][:2], d["keep_W"], d["keep_b"])
+    dev_loss = float(np.abs(lv.astype(np.float64) - d["ref"][2])[d["row_ok"]].max(initial=0.0))
+    print(f"\nunaligned {which}, case {fc.CASE_IDS[i]}: kernel {dev:.3e} E32 {d['e32']:.3e} ratio {dev / d['e32']:.2f} | "
+          f"loss kernel {dev_loss:.3e} E32 {d['e32_loss']:.3e} ratio {dev_loss / d['e32_loss']:.2f}")
+    empty = np.diff(case["ptr"]) == 0
+    assert W[empty].tobytes() == case["W0"][empty].tobytes() and b[empty].tobytes() == case["b0"][empty].tobytes()
+    assert (lv[empty] == 0).all()
+    assert np.isfinite(W).all() and np.isfinite(b).all() and np.isfinite(lv).all()
+    assert dev <= 2 * d["e32"]
+    assert dev_loss <= 2 * d["e32_loss"]
+    if case["dim"] == 24:
+        for got, want in zip((W, b, lv), run_entry(case, d["loss"], d["steps"], d["wd"], 0, 0)):
+            assert got.tobytes() == want.tobytes()
 
 
 @pytest.mark.parametrize("dim, n_neg, loss", [(16, 3, "pointwise"), (65, 5, "adaptive_hinge"), (128, 1, "bpr")])

@@ -132,6 +132,35 @@ def test_no_gradient_case_sits_on_a_kink_and_every_feature_is_present():
     assert not data["r64"]["aE"][0].any() and (data["r64"]["aE"] >= np.abs(data["r64"]["gE"]) * (1 - 1e-12)).all()
 
 
+@pytest.mark.parametrize("name, d, loss", sc.EDGE_CASES)
+def test_no_edge_case_sits_on_a_kink_and_each_holds_its_edge(name, d, loss):
+    case = sc.edge_case(name, d)
+    assert sc.kink_margin(case, loss) > fc.TIE
+    seq, neg, N = case["seq"], case["neg"], case["num_items"]
+    assert seq.min() >= 0 and seq.max() < N and neg.min() >= 0 and neg.max() < N
+    items = (seq != 0).sum(1)
+    if name in ("scatter", "inside"):
+        # zeros among the items, not only on the left; a row ending in one; no row of padding alone
+        first = (seq != 0).argmax(1)
+        assert sum((seq[r, first[r]:] == 0).any() for r in range(len(seq))) > len(seq) // 2
+        assert seq[0, -1] == 0 and (items >= 1).all()
+    if name == "inside":
+        out = sc.edge_case("outside", d)
+        bad = sc.outside_ids(N)
+        assert np.isin(out["seq"][seq == 0], bad).all() and (out["seq"][seq != 0] == seq[seq != 0]).all()
+        moved = out["neg"] != neg
+        assert moved.mean() > 0.05 and np.isin(out["neg"][moved], bad).all() and (neg[moved] == 0).all()
+        for b in bad:
+            assert (out["seq"] == b).any() and (out["neg"] == b).any()
+    if name == "empty":
+        assert items[4] == 0 and items[8] == 0 and len(seq) == 9 and (np.delete(items, [4, 8]) >= 1).all()
+    if name == "maxlen":
+        assert seq.shape == (3, seq_engine.SEQ_MAX_LEN) and neg.shape[0] == seq_engine.SEQ_MAX_NEG
+        assert items.tolist() == [1024, 512, 1]
+    data = sc.edge_data(name, d, loss)
+    assert data["e32"] > 0 and not data["r64"]["gE"][0].any() and data["r64"]["gb"][0] == 0
+
+
 def test_generate_sequential_is_seeded_and_keeps_id_zero_free():
     a = generate_sequential(20, 30, 400, 0.01, 1, np.random.RandomState(5))
     b = generate_sequential(20, 30, 400, 0.01, 1, np.random.RandomState(5))

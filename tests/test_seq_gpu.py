@@ -2,7 +2,9 @@
 fold_in_common's rule (tests/seq_common.py), rg_seq_adam_dense against torch's op sequence, five
 free-running steps beside the float64 oracle, rg_seq_pool_repr / predict / recommend_next against
 the fixture and the oracle, sequence_mrr_score's device path against its host loop, the entries'
-refusals, and an end-to-end fit.  Every case in a few seconds.
+refusals, and an end-to-end fit; the kernels again on tables that start off a 16-byte boundary, the
+Adam pass on a table larger than one trip of its grid, and the entries' stated edges (padding
+anywhere, ids outside the table, empty sequences, L = 1024 with K = 16).  Every case in a few seconds.
 """
 import ctypes
 
@@ -56,11 +58,51 @@ def test_the_loss_is_the_same_bits_on_every_run():
         assert np.abs(g.cpu().numpy() - g0).max() <= 1e-5 * np.abs(g0).max()
 
 
-@pytest.mark.parametrize("l2", [0.0, 1e-3])
-@pytest.mark.parametrize("step", [1, 7])
-def test_adam_dense_is_torchs_op_sequence(step, l2):
+GUARD = 64
+
+
+def _view(host, off, guard=GUARD):
+    """``host`` as a contiguous device view ``off`` floats into a buffer of -7 (guards on both
+    sides): returns (buffer, view)."""
+    host = np.ascontiguousarray(host)
+    buf = torch.full((off + host.size + guard,), -7.0, dtype=torch.float32, device=DEV)
+    view = buf[off:off + host.size].view(host.shape)
+    view.copy_(torch.from_numpy(host))
+    assert view.is_contiguous() and view.data_ptr() % 16 == 4 * off
+    return buf, view
+
+
+def _guards_hold(buf, off, size):
+    got = buf.cpu().numpy()
+    return (got[:off] == -7.0).all() and (got[off + size:] == -7.0).all()
+
+
+@pytest.mark.parametrize("i", sc.UNALIGNED, ids=[sc.CASE_IDS[i] for i in sc.UNALIGNED])
+def test_pool_grads_on_a_table_off_a_16_byte_boundary(i):
+    """The unaligned dispatch (dispatch_seq's scalar layouts) under the oracle test's own rule; at
+    d 24 the aligned call selects the same layout, so the loss (fixed-order sums) has its bits."""
+    data = sc.case_data(i)
+    case, loss, d = data["case"], data["loss"], data["case"]["d"]
+    ebuf, E = _view(case["E"], 1)
+    lv, grad = seq_engine.pool_grads(E, _dev(case["b"]), _dev(case["seq"]), _dev(case["neg"]), loss)
+    lv32, lv, grad = lv.cpu().numpy(), float(lv), grad.cpu().numpy()
+    assert ebuf.cpu().numpy()[1:1 + E.numel()].tobytes() == case["E"].tobytes() and _guards_hold(ebuf, 1, E.numel())
+    ref = data["r64"]
+    rel_loss = abs(lv - ref["loss"]) / abs(ref["loss"])
+    worst, plain = sc.gradient_excess(grad[:, :d], grad[:, d], data)
+    print(f"\nunaligned E, case {sc.CASE_IDS[i]}: loss rel {rel_loss:.2e} | gradient: E32 {data['e32']:.3e} "
+          f"kernel / E32 {plain:.2f} kernel / bound {worst:.3f}")
+    assert np.isfinite(grad).all() and not grad[0].any()
+    assert rel_loss <= 1e-5
+    assert worst <= 1.0
+    if d == 24:
+        lv0, _ = seq_engine.pool_grads(_dev(case["E"]), _dev(case["b"]), _dev(case["seq"]), _dev(case["neg"]), loss)
+        assert lv0.cpu().numpy().tobytes() == lv32.tobytes()
+
+
+def _adam_dense_against_torchs_op_sequence(N, d, step, l2, what):
     rs = np.random.RandomState(10 * step + int(l2 > 0))
-    N, d, lr = 301, 20, 1e-2
+    lr = 1e-2
     E, b = sc.make_tables(N, d, rs)
     g = (rs.randn(N, d + 1) * 1e-3).astype(np.float32)
     g[5] *= 1e-6                                              # |g| near eps
@@ -82,12 +124,37 @@ def test_adam_dense_is_torchs_op_sequence(step, l2):
         up = np.minimum(sc.ulps(got[keys[0]][1:], refs[0][0].numpy()[1:]), sc.ulps(got[keys[0]][1:], refs[1][0].numpy()[1:]))
         um = sc.ulps(got[keys[1]][1:], refs[0][1].numpy()[1:])
         uv = sc.ulps(got[keys[2]][1:], refs[0][2].numpy()[1:])
-        print(f"\nadam step {step} l2 {l2} {name}: max ulp p {up.max()} m {um.max()} v {uv.max()}")
+        print(f"\nadam{what} step {step} l2 {l2} {name}: max ulp p {up.max()} m {um.max()} v {uv.max()}")
         assert up.max() <= 1 and um.max() <= 1 and uv.max() <= 1
         # row 0 is untouched, parameters and moments
         for k, start in zip(keys, (p0, m0, v0)):
             assert got[k][0].tobytes() == np.ascontiguousarray(start[0]).tobytes()
         assert (got[keys[0]][1:] != p0[1:]).any()
+    return E, b, got
+
+
+@pytest.mark.parametrize("l2", [0.0, 1e-3])
+@pytest.mark.parametrize("step", [1, 7])
+def test_adam_dense_is_torchs_op_sequence(step, l2):
+    _adam_dense_against_torchs_op_sequence(301, 20, step, l2, "")
+
+
+@pytest.mark.parametrize("step", [1, 7])
+def test_adam_dense_beyond_one_trip_of_the_grid(step):
+    """seq_adam_kernel launches at most 8 * CUs blocks of 256 threads, which stride over the
+    num_items * (d + 1) elements: a table with more elements than that sends threads on a second
+    trip (here 60 rows' worth of them), with element numbers past 2^19 split into row and column."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    d, one_trip = 256, 8 * cus * 256
+    N = one_trip // (d + 1) + 60
+    assert N * (d + 1) > one_trip
+    E, b, got = _adam_dense_against_torchs_op_sequence(N, d, step, 1e-3, f" {N} x {d + 1} > {one_trip}")
+    # the last row, and the last columns of every row behind the first trip, were updated (an update
+    # below half an ulp of its parameter is possible, so nearly all of them rather than all)
+    later = one_trip // (d + 1) + 1
+    assert later * (d + 1) >= one_trip and N - later >= 50
+    assert (got["E"][N - 1] != E[N - 1]).mean() > 0.99 and got["b"][N - 1] != b[N - 1]
+    assert (got["E"][later:, d - 1] != E[later:, d - 1]).mean() > 0.9 and (got["b"][later:] != b[later:]).mean() > 0.9
 
 
 def test_five_free_running_steps_beside_the_float64_oracle():
@@ -156,7 +223,151 @@ def test_pool_repr_and_predict_reproduce_the_reference_fixture():
         assert some.tobytes() == p[[3, 1, 22]].tobytes()
 
 
-@pytest.mark.parametrize("n, L, d", [(1, 1, 8), (3, 33, 64), (300, 33, 12), (300, 1, 256), (3, 1, 4), (1, 33, 128)])
+def repr_entry(E, ids, ptr, L, n, out, num_items):
+    """rg_seq_pool_repr itself (``pool_repr`` makes its own aligned ``out`` and checks the ids)."""
+    lib, p = _lib.load(), _lib.ptr
+    rc = lib.rg_seq_pool_repr(_lib.stream_handle(), p(E), int(E.shape[1]), num_items, p(ids), p(ptr), L, n, p(out))
+    assert rc == 0, lib.rg_last_error()
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("which", ["E and out", "out alone"])
+@pytest.mark.parametrize("d", [8, 16, 64, 128, 24])
+def test_pool_repr_on_tables_off_a_16_byte_boundary(d, which):
+    """The unaligned dispatch (dispatch_seq's scalar layouts) inside the oracle test's own bound,
+    padded and ragged; at d 24 the aligned call selects the same layout and gives the same bits."""
+    n, L, N = 67, 33, 257
+    rs = np.random.RandomState(n + L + d)
+    E, _ = sc.make_tables(N, d, rs)
+    seq = sc.make_sequences(n, L, N, rs)
+    _, ref = sc.representations(torch.from_numpy(E).double(), torch.from_numpy(seq))
+    ref = ref.numpy()
+    bound = (L + 1) * EPS32 * np.abs(E).max() + 1e-30
+    ptr, ids = _ragged(seq)
+    off_e = 1 if which == "E and out" else 0
+    ebuf, Ed = _view(E, off_e)
+    for form, args in (("padded", (_dev(seq), None, L)), ("ragged", (_dev(ids), _dev(ptr), 0))):
+        obuf, out = _view(np.zeros((n, d), np.float32), 1)
+        repr_entry(Ed, *args, n, out, N)
+        R = out.cpu().numpy()
+        err = np.abs(R - ref).max()
+        print(f"\nunaligned {which}, d {d} {form}: max err {err:.3e} bound {bound:.3e} ratio {err / bound:.3f}")
+        assert _guards_hold(obuf, 1, out.numel()) and _guards_hold(ebuf, off_e, Ed.numel())
+        assert err <= bound
+        if d == 24:
+            aligned = torch.empty(n, d, device=DEV)
+            repr_entry(_dev(E), *args, n, aligned, N)
+            assert aligned.cpu().numpy().tobytes() == R.tobytes()
+    assert ebuf.cpu().numpy()[off_e:off_e + Ed.numel()].tobytes() == E.tobytes()
+
+
+@pytest.mark.parametrize("name, d, loss", sc.EDGE_CASES)
+def test_pool_grads_at_the_entrys_edges_against_the_float64_oracle(name, d, loss):
+    """Padding anywhere in a sequence (one row ends in it), zeros where the next test puts ids outside
+    the table, rows of padding alone, and L = 1024 with K = 16 (the workspace's largest strides):
+    each under the oracle test's own rule.  The longest case is followed by its representations."""
+    data = sc.edge_data(name, d, loss)
+    case = data["case"]
+    N = case["num_items"]
+    E = _dev(case["E"])
+    lv, grad = seq_engine.pool_grads(E, _dev(case["b"]), _dev(case["seq"]), _dev(case["neg"]), loss)
+    lv, grad = float(lv), grad.cpu().numpy()
+    ref = data["r64"]
+    rel_loss = abs(lv - ref["loss"]) / abs(ref["loss"])
+    worst, plain = sc.gradient_excess(grad[:, :d], grad[:, d], data)
+    print(f"\nedge {name} d {d} {loss}: loss rel {rel_loss:.2e} | gradient: E32 {data['e32']:.3e} "
+          f"kernel / E32 {plain:.2f} kernel / bound {worst:.3f}")
+    assert np.isfinite(grad).all() and not grad[0].any()
+    assert rel_loss <= 1e-5
+    assert worst <= 1.0
+    seq = case["seq"]
+    if name == "empty":
+        # a row of padding alone adds no partial: without the last row (one of them) the partials
+        # before it stand where they stood and the loss has the same bits
+        a = seq_engine.pool_grads(E, _dev(case["b"]), _dev(seq), _dev(case["neg"]), loss)[0]
+        b = seq_engine.pool_grads(E, _dev(case["b"]), _dev(seq[:-1]), _dev(case["neg"][:, :-1]), loss)
+        assert a.cpu().numpy().tobytes() == b[0].cpu().numpy().tobytes()
+        g2 = b[1].cpu().numpy().astype(np.float64)
+        assert np.abs(g2 - grad).max() <= 1e-5 * np.abs(grad).max()
+    # the same sequences through rg_seq_pool_repr, padded and ragged
+    L = seq.shape[1]
+    _, r64 = sc.representations(torch.from_numpy(case["E"]).double(), torch.from_numpy(seq))
+    bound = (L + 1) * EPS32 * np.abs(case["E"]).max() + 1e-30
+    ptr, ids = _ragged(seq)
+    for form, R in (("padded", seq_engine.pool_repr(E, _dev(seq))),
+                    ("ragged", seq_engine.pool_repr(E, _dev(ids), seq_ptr=ptr))):
+        err = np.abs(R.cpu().numpy() - r64.numpy()).max()
+        print(f"edge {name} d {d} representations {form}: max err {err:.3e} bound {bound:.3e} ratio {err / bound:.3f}")
+        assert err <= bound
+        assert not R.cpu().numpy()[(seq != 0).sum(1) == 0].any()
+
+
+@pytest.mark.parametrize("d, loss", [(8, "hinge"), (64, "bpr")])
+def test_ids_outside_the_table_are_read_as_padding(d, loss):
+    """include/rg_hip.h: "an id outside [0, num_items) is read as padding".  The padding zeros of
+    seq and a tenth of neg become num_items, num_items + 5, -1 and 2^40; inv_count stays the
+    caller's count of the ids in range.  The fixed-order sums (loss, representations) have the bits
+    of the call with zeros there, the atomic gradient agrees to rounding, and neither the guard
+    rows behind grad nor E's buffer change."""
+    out, ins = sc.edge_case("outside", d), sc.edge_case("inside", d)
+    N, rows = out["num_items"], 3
+    count = int((ins["seq"] != 0).sum())
+    assert count == int(((out["seq"] > 0) & (out["seq"] < N)).sum())
+    ebuf, E = _view(out["E"], 0, guard=rows * d)
+    b = _dev(out["b"])
+    got = []
+    for case in (out, ins):
+        gbuf = torch.full(((N + rows) * (d + 1),), -7.0, dtype=torch.float32, device=DEV)
+        grad = gbuf[:N * (d + 1)].view(N, d + 1).zero_()
+        lv, _ = seq_engine.pool_grads(E, b, _dev(case["seq"]), _dev(case["neg"]), loss, grad=grad, mask_count=count,
+                                      checked=True)
+        torch.cuda.synchronize()
+        assert (gbuf[N * (d + 1):].cpu().numpy() == -7.0).all(), "rows behind grad written"
+        got.append((lv.cpu().numpy(), grad.cpu().numpy()))
+    assert got[0][0].tobytes() == got[1][0].tobytes()
+    g_out, g_in = got[0][1].astype(np.float64), got[1][1].astype(np.float64)
+    assert not g_out[0].any() and np.abs(g_out - g_in).max() <= 1e-5 * np.abs(g_in).max()
+    # the call with zeros there is itself held to the oracle (the edge test above); so is this one
+    data = sc.edge_data("inside", d, loss)
+    worst, plain = sc.gradient_excess(got[0][1][:, :d], got[0][1][:, d], data)
+    print(f"\nids outside d {d} {loss}: gradient: E32 {data['e32']:.3e} kernel / E32 {plain:.2f} "
+          f"kernel / bound {worst:.3f}")
+    assert worst <= 1.0
+    ptr, _ = _ragged(ins["seq"])
+    kept = out["seq"][ins["seq"] != 0]
+    for a, z in ((seq_engine.pool_repr(E, _dev(out["seq"]), checked=True), seq_engine.pool_repr(E, _dev(ins["seq"]))),
+                 (seq_engine.pool_repr(E, _dev(out["seq"].reshape(-1)), seq_ptr=np.arange(len(ptr)) * out["L"],
+                                       checked=True),
+                  seq_engine.pool_repr(E, _dev(kept), seq_ptr=ptr))):
+        assert a.cpu().numpy().tobytes() == z.cpu().numpy().tobytes()
+    eb = ebuf.cpu().numpy()
+    assert eb[:E.numel()].tobytes() == out["E"].tobytes() and (eb[E.numel():] == -7.0).all()
+
+
+def test_pool_repr_gives_empty_sequences_the_zero_row():
+    """include/rg_hip.h: "an empty sequence gives the zero row" -- ragged with the first, a middle
+    and the last sequence empty, padded with rows of zeros, and a call of empty sequences alone."""
+    d, N, n, L = 24, 40, 9, 5
+    rs = np.random.RandomState(3)
+    E, _ = sc.make_tables(N, d, rs)
+    seq = sc.make_sequences(n, L, N, rs)
+    seq[[0, 4, 8]] = 0
+    _, ref = sc.representations(torch.from_numpy(E).double(), torch.from_numpy(seq))
+    bound = (L + 1) * EPS32 * np.abs(E).max() + 1e-30
+    ptr, ids = _ragged(seq)
+    assert ptr[0] == ptr[1] and ptr[4] == ptr[5] and ptr[8] == ptr[9] == len(ids)
+    Ed = _dev(E)
+    for R in (seq_engine.pool_repr(Ed, _dev(seq)), seq_engine.pool_repr(Ed, _dev(ids), seq_ptr=ptr)):
+        R = R.cpu().numpy()
+        assert R[[0, 4, 8]].tobytes() == np.zeros((3, d), np.float32).tobytes()
+        assert R[[1, 2, 3, 5, 6, 7]].any(axis=1).all() and np.abs(R - ref.numpy()).max() <= bound
+    R = seq_engine.pool_repr(Ed, _dev(np.zeros(0, np.int64)), seq_ptr=np.zeros(4, np.int64)).cpu().numpy()
+    assert R.tobytes() == np.zeros((3, d), np.float32).tobytes()
+
+
+@pytest.mark.parametrize("n, L, d", [(1, 1, 8), (3, 33, 64), (300, 33, 12), (300, 1, 256), (3, 1, 4), (1, 33, 128),
+                                     (3, 33, 16), (300, 5, 32), (3, 5, 24), (300, 33, 48), (3, 33, 96), (300, 2, 160),
+                                     (3, 5, 200)])
 def test_pool_repr_and_predict_batch_against_the_oracle(n, L, d):
     rs = np.random.RandomState(n + L + d)
     N = 257
