@@ -299,7 +299,9 @@ struct RowLayout {
 #pragma unroll
             for (int e = 0; e < EPL; ++e) {
                 const int c = sub + LPU * e;
-                if (c < D) __builtin_amdgcn_raw_buffer_store_b32(v[e], rs, (int)((row * D + c) * 4), 0, kSc1);
+                // the builtin takes the dword as an unsigned int: pass the float's bits, not its value
+                if (c < D)
+                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[e]), rs, (int)((row * D + c) * 4), 0, kSc1);
             }
         }
     }
@@ -321,7 +323,9 @@ struct RowLayout {
 #pragma unroll
             for (int e = 0; e < EPL; ++e) {
                 const int c = sub + LPU * e;
-                v[e] = c < D ? __builtin_amdgcn_raw_buffer_load_b32(rs, (int)((row * D + c) * 4), 0, kSc1) : 0.0f;
+                // the builtin returns the dword as an unsigned int: take its bits, not its value
+                v[e] = c < D ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (int)((row * D + c) * 4), 0, kSc1))
+                             : 0.0f;
             }
         }
     }

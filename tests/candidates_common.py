@@ -1,6 +1,26 @@
 """What the candidate-list tests share (no tests here): the ragged cases for rg_seg_topk / rg_seg_rank
 with their numpy references, the MF tables and the error bound of rg_mf_score_lists, the float64
-reference behind the model-level comparison with ``recommend``, and the stub models of the CPU tests."""
+reference behind the model-level comparison with ``recommend``, and the stub models of the CPU tests.
+
+rg_mf_score_lists picks its row layout from ``dim`` and from whether both tables are 16-byte aligned
+(dispatch_lists, csrc/rg_cand.hip): fifteen layouts, each selected by a dim of SCORE_DIMS, whose test
+runs every multiple of 4 both aligned and on views one float off.
+
+  aligned tables, dim % 4 == 0
+    the pair kernel's float4 layouts at their own sizes   8, 16, 32, 64, 128, 256
+    VecLayout<16>  (other multiples of 4 up to 64)         12, 24, 60
+    VecLayout<32>  (up to 128)                             68, 124
+    VecLayout<64>  (up to 256)                             132, 160, 192, 252
+  scalar loads (dim % 4 != 0, or an unaligned table): lane sub holds columns sub + LPU * e, c < dim
+    <16,1>  dims 1..16      1, 3;     unaligned 8, 12, 16
+    <16,2>  dims 17..32     17;       unaligned 24, 32
+    <16,4>  dims 33..64               unaligned 60, 64
+    <64,2>  dims 65..128    65;       unaligned 68, 124, 128
+    <64,3>  dims 129..192   129, 191; unaligned 132, 160, 192
+    <64,4>  dims 193..256             unaligned 252, 256
+
+12 / 60, 68 / 124 and 132 / 252 are the first and last multiple of 4 of a VecLayout's range that is
+not a float4 size (one live lane, one dead lane); 17, 129 and 191 never take float4 loads."""
 import numpy as np
 import torch
 
@@ -78,7 +98,8 @@ def take_lists(scores, ptr, idx, rows):
 
 
 # ---------------------------------------------------------------- rg_mf_score_lists
-SCORE_DIMS = [1, 3, 16, 64, 65, 256]
+SCORE_DIMS = [1, 3, 16, 64, 65, 256] + [12, 60, 68, 124, 132, 252] + [8, 32, 128] + [24, 160, 192] + [17, 129, 191]
+VEC_LAYOUT_DIMS = {"VecLayout<16>": 24, "VecLayout<32>": 100, "VecLayout<64>": 160}   # one dim per VecLayout
 SCORE_USERS = [1, 5, 130]
 
 
@@ -108,6 +129,20 @@ def mf_reference(tables, users, ptr, idx):
     rows = np.repeat(np.arange(len(users)), np.diff(ptr))
     u, i = users[rows], idx.astype(np.int64)
     return ref, mf_bound(U.numpy()[u], I.numpy()[i], ub.numpy()[u], ib.numpy()[i])
+
+
+def mf_scores_float32(tables, users, ptr, idx):
+    """rg_mf_score_lists restated in float32 numpy: the products summed in one chain of length dim in
+    column order (no fma, the longest chain any layout has), then the biases, then the sigmoid."""
+    U, I, ub, ib = (np.asarray(t, dtype=np.float32) for t in tables)
+    rows = np.repeat(np.arange(len(users)), np.diff(ptr))
+    u, i = users[rows], idx.astype(np.int64)
+    z = np.zeros(len(i), np.float32)
+    for k in range(U.shape[1]):
+        z = z + U[u, k] * I[i, k]
+    z = (z + ub[u]) + ib[i]
+    assert z.dtype == np.float32
+    return (np.float32(1.0) / (np.float32(1.0) + np.exp(-z))).astype(np.float32)
 
 
 def mf_bound(p, q, b, c):

@@ -157,6 +157,23 @@ def test_sampled_protocol_tables_of_the_gpu_test():
     assert ((zl[:, 1:] == zl[:, :1]).any(axis=1)).mean() > 0.5
 
 
+@pytest.mark.parametrize("dim", cc.SCORE_DIMS)
+def test_mf_reference_admits_a_float32_restatement(dim):
+    """The float64 reference and the bound the GPU test holds rg_mf_score_lists to, on the GPU test's
+    own tables and lists at every dim of SCORE_DIMS: a plain float32 numpy restatement of the formula
+    (one summation chain of length dim, longer than any layout's) stays inside the bound."""
+    tables = cc.mf_tables(dim)
+    worst = 0.0
+    for n_lists in cc.SCORE_USERS:
+        users, ptr, idx = cc.score_case(n_lists, seed=n_lists)
+        ref, bound = cc.mf_reference(tables, users, ptr, idx)
+        got = cc.mf_scores_float32(tables, users, ptr, idx)
+        assert got.shape == ref.shape and len(ref) > 0
+        worst = max(worst, float((np.abs(got.astype(np.float64) - ref) / bound).max()))
+    print(f"\ndim {dim}: float32 restatement, largest share of the bound {worst:.3f}")
+    assert worst <= 1.0
+
+
 # ---------------------------------------------------------------- the entries, without a GPU
 def test_signatures_are_bound():
     sig = {n: a for n, _, a in _lib.SIGNATURES}

@@ -125,7 +125,25 @@ def test_mf_score_lists_within_the_derived_bound(dim):
     print(f"dim {dim}: largest share of the bound over all cases {worst:.3f}")
 
 
-@pytest.mark.parametrize("dim", [3, 16, 65, 100])
+@pytest.mark.parametrize("dim", sorted(cc.VEC_LAYOUT_DIMS.values()))
+def test_aligned_and_unaligned_calls_both_meet_the_float64_reference(dim):
+    """One dim per VecLayout (24, 100, 160): the aligned call runs on the VecLayout, the call on views
+    one float off on the scalar layout of the same range (<16,2>, <64,2>, <64,3>).  The two order the
+    summation chain differently, so the bits may differ; each is held to the bound against float64,
+    and so they lie within two bounds of each other."""
+    tables = cc.mf_tables(dim, seed=2)
+    users, ptr, idx = cc.score_case(130, seed=11)
+    ref, bound = cc.mf_reference(tables, users, ptr, idx)
+    got = [run_scores(tables, users, ptr, idx, unaligned).astype(np.float64) for unaligned in (False, True)]
+    shares = [float((np.abs(g - ref) / bound).max()) for g in got]
+    between = float((np.abs(got[0] - got[1]) / bound).max())
+    print(f"\ndim {dim}: largest share of the bound, aligned {shares[0]:.3f}, unaligned {shares[1]:.3f}; "
+          f"|aligned - unaligned| / bound {between:.3f}")
+    assert shares[0] <= 1.0 and shares[1] <= 1.0
+    assert between <= 2.0
+
+
+@pytest.mark.parametrize("dim", [3, 16, 65, 100, 12, 132])
 def test_a_pairs_score_is_the_same_bits_wherever_it_stands(dim):
     tables = cc.mf_tables(dim)
     users, ptr, idx = cc.score_case(130, seed=7)

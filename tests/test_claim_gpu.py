@@ -66,7 +66,9 @@ def _run(dev, claim, tabs, pool_u, pool_i, steps, loss, opt, n, B, mt, plan=True
 
 @pytest.mark.parametrize("loss,opt,d,plan", [("bpr", "adam", 64, True), ("pointwise", "adam", 32, True),
                                              ("hinge", "rms", 64, False), ("bpr", "sgd", 128, True),
-                                             ("pointwise", "adam", 50, False), ("bpr", "adam", 8, True)])
+                                             ("pointwise", "adam", 50, False), ("bpr", "adam", 8, True),
+                                             # the scalar layouts <16,2> and <64,3>
+                                             ("bpr", "adam", 24, False), ("pointwise", "adam", 160, True)])
 def test_claimed_slots_equal_pair_pass_atomics(dev, loss, opt, d, plan):
     U, I, B, n = 3000, 400, 256, 5
     tabs, pool_u, pool_i, steps = _case(U, I, d, B, 12, 20000, seed=d + len(loss))

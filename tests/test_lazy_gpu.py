@@ -89,7 +89,8 @@ def _same(a, b, what):
 @pytest.mark.parametrize("loss,opt,d", [("bpr", "adam", 64), ("pointwise", "adam", 32), ("hinge", "rms", 64),
                                         ("adaptive_hinge", "adam", 64), ("bpr", "sgd", 128),
                                         ("pointwise", "adam", 50), ("bpr", "adam", 8),
-                                        ("adaptive_hinge", "adam", 8)])
+                                        ("adaptive_hinge", "adam", 8),
+                                        ("bpr", "adam", 24), ("pointwise", "adam", 160)])   # <16,2>, <64,3>
 def test_lazy_equals_eager_bitwise(dev, loss, opt, d):
     U, I, B, n = 3000, 400, 256, 5
     tabs, pool_u, pool_i, steps = _case(U, I, d, B, 14, 20000, seed=d + len(loss))

@@ -13,6 +13,7 @@ import torch
 
 from oracle import mf as omf
 from oracle import rng as orng
+from tests import mf_layout_common as lc
 
 pytestmark = pytest.mark.gpu
 
@@ -30,6 +31,8 @@ def close(got, ref, rtol=RTOL, what=""):
     assert got.shape == ref.shape, (what, got.shape, ref.shape)
     scale = float(np.max(np.abs(ref))) if ref.size else 0.0
     np.testing.assert_allclose(got, ref, rtol=rtol, atol=rtol * max(scale, 1e-30), err_msg=what)
+    # the share of the allowance used (reporting only)
+    return float(np.max(np.abs(got - ref) / (rtol * np.abs(ref) + rtol * max(scale, 1e-30)))) if ref.size else 0.0
 
 
 def close_adam(got, ref32, ref64, what="", small=False):
@@ -47,8 +50,19 @@ def close_adam(got, ref32, ref64, what="", small=False):
     to ~1e-9 takes Adam's first step g / (|g| + eps) ~ g / eps, which turns the 1-ulp
     differences of dz (the device expf vs torch's vectorised exp, FMA contraction) into
     ~1e-5 of the vector's norm, while the fp32 reference happens to sit 1.3e-6 from fp64."""
-    ok, msg = omf.tensor_parity(got, ref32, ref64, rtol=1e-5, band=15.0 if small else 3.0)
+    band = 15.0 if small else 3.0
+    ok, msg = omf.tensor_parity(got, ref32, ref64, rtol=1e-5, band=band)
     assert ok, f"{what}: {msg}"
+    return adam_share(got, ref32, ref64, band)
+
+
+def adam_share(got, ref32, ref64, band, rtol=1e-5):
+    """How much of tensor_parity's allowance ``got`` uses (reporting only; the verdict is
+    tensor_parity's own): (relative norm against ref32 / rtol, distance from ref64 / its band)."""
+    g, r, r64 = (torch.as_tensor(x).double().reshape(-1).cpu() for x in (got, ref32, ref64))
+    a = float((g - r).norm()) / (rtol * max(float(r.norm()), 1e-30))
+    b = float((g - r64).norm()) / max(band * float((r - r64).norm()) + 0.1 * rtol * float(r64.norm()), 1e-300)
+    return a, b
 
 
 def close_norm(got, ref, rtol=RTOL, what=""):
@@ -149,16 +163,63 @@ def make_case(U, I, d, B, n, P, seed, hot_items=False):
     return (Uw, Iw, ub, ib), pool_u, pool_i, steps
 
 
-def run_parity(dev, U, I, d, B, n, loss, opt, wd=1e-5, seed=0, hot=False, P=5000, lr=1e-2, plan=False):
-    from recommendation_gans_amd.mf_engine import MFEngine
+class Shares:
+    """The largest share of each criterion's allowance that a run used (reporting only): ``rel`` the
+    relative norm against close_adam's 1e-5, ``band`` the distance from float64 against its band on
+    the tensors that needed it, ``elem`` the elementwise share of close's allowance."""
+
+    def __init__(self):
+        self.rel, self.band, self.elem = 0.0, 0.0, 0.0
+
+    def adam(self, share):
+        a, b = share
+        if a <= 1.0:
+            self.rel = max(self.rel, a)
+        else:                       # past 1e-5 relative: tensor_parity passed it on the band
+            self.band = max(self.band, b)
+
+    def __str__(self):
+        return f"rel/1e-5 {self.rel:.3f}, band share {self.band:.3f}, elementwise share {self.elem:.3f}"
+
+
+def check_step(tag, opt, got_loss, got_params, got_m, got_v, o, o64, ref_loss, shares):
+    """The criterion of one step of run_parity: the loss by ``close``; every table, and Adam's m
+    and Adam's / RMSprop's v, by ``close_adam`` (SGD: ``close``) against the fp32 oracle ``o`` and
+    the float64 oracle ``o64``.  The GPU's result and (tests/test_parity_cpu.py) another fp32
+    summation order of the oracle itself go through this same function."""
+    shares.elem = max(shares.elem, close(got_loss, np.float32(ref_loss), what=tag + " loss"))
+    for k, nm in enumerate(("user_w", "item_w", "user_b", "item_b")):
+        shp = got_params[k].shape
+        if opt == "sgd":
+            shares.elem = max(shares.elem, close(got_params[k], o.params[k].reshape(shp), what=f"{tag} {nm}"))
+        else:
+            shares.adam(close_adam(got_params[k], o.params[k].reshape(shp), o64.params[k].reshape(shp),
+                                   what=f"{tag} {nm}", small=k >= 2))
+        if opt == "adam":
+            shares.adam(close_adam(got_m[k], o.opt.state[k][0].reshape(shp), o64.opt.state[k][0].reshape(shp),
+                                   what=f"{tag} m {nm}", small=k >= 2))
+        if opt != "sgd":
+            shares.adam(close_adam(got_v[k], o.opt.state[k][1].reshape(shp), o64.opt.state[k][1].reshape(shp),
+                                   what=f"{tag} v {nm}", small=k >= 2))
+
+
+def make_oracles(U, I, d, B, n, loss, opt, wd=1e-5, seed=0, hot=False, P=5000, lr=1e-2, order_seeds=(None,)):
+    """(tables, pool, steps, MT state, [fp32 oracle per order seed], float64 oracle) of a run_parity case."""
     tabs, pool_u, pool_i, steps = make_case(U, I, d, B, n, P, seed, hot_items=hot)
     st = orng.py_seed_state(100 + seed)
-    o = omf.MFOracle(*[t.clone() for t in tabs], pool_u, pool_i, st.copy(), loss=loss, optimizer=opt, lr=lr,
-                     weight_decay=wd, n_neg=n, batch_size=B)
-    o64 = omf.MFOracle(*[t.clone().double() for t in tabs], pool_u, pool_i, st.copy(), loss=loss, optimizer=opt,
-                       lr=lr, weight_decay=wd, n_neg=n, batch_size=B)
+    kw = dict(loss=loss, optimizer=opt, lr=lr, weight_decay=wd, n_neg=n, batch_size=B)
+    o32 = [omf.MFOracle(*[t.clone() for t in tabs], pool_u, pool_i, st.copy(), order_seed=os_, **kw)
+           for os_ in order_seeds]
+    o64 = omf.MFOracle(*[t.clone().double() for t in tabs], pool_u, pool_i, st.copy(), **kw)
+    return tabs, pool_u, pool_i, steps, st, o32, o64
+
+
+def run_parity(dev, U, I, d, B, n, loss, opt, wd=1e-5, seed=0, hot=False, P=5000, lr=1e-2, plan=False):
+    from recommendation_gans_amd.mf_engine import MFEngine
+    tabs, pool_u, pool_i, steps, st, (o,), o64 = make_oracles(U, I, d, B, n, loss, opt, wd, seed, hot, P, lr)
     e = MFEngine(tabs[0], tabs[1], tabs[2].reshape(-1), tabs[3].reshape(-1), pool_u, pool_i, st.copy(), loss=loss,
                  optimizer=opt, lr=lr, weight_decay=wd, n_neg=n, batch_size=B, device=dev)
+    shares = Shares()
     for s, (pu, pi) in enumerate(steps):
         ref_loss = o.step(pu, pi)
         o64.step(pu, pi)
@@ -166,24 +227,13 @@ def run_parity(dev, U, I, d, B, n, loss, opt, wd=1e-5, seed=0, hot=False, P=5000
         got = e.train_step(du, di, plan=e.make_plan(di) if plan else None)
         torch.cuda.synchronize()
         tag = f"{loss}/{opt}/d{d}/step{s}{'/plan' if plan else ''}"
-        close(got[0], np.float32(ref_loss), what=tag + " loss")
-        for k, nm in enumerate(("user_w", "item_w", "user_b", "item_b")):
-            shp = e.params()[k].shape
-            if opt == "sgd":
-                close(e.params()[k], o.params[k].reshape(shp), what=f"{tag} {nm}")
-            else:
-                close_adam(e.params()[k], o.params[k].reshape(shp), o64.params[k].reshape(shp), what=f"{tag} {nm}",
-                           small=k >= 2)
-            if opt == "adam":
-                close_adam(e.m[k], o.opt.state[k][0].reshape(shp), o64.opt.state[k][0].reshape(shp),
-                           what=f"{tag} m {nm}", small=k >= 2)
-            if opt != "sgd":
-                close_adam(e.v[k], o.opt.state[k][1].reshape(shp), o64.opt.state[k][1].reshape(shp),
-                           what=f"{tag} v {nm}", small=k >= 2)
+        check_step(tag, opt, got[0], e.params(), e.m, e.v, o, o64, ref_loss, shares)
         assert (e.mt_state() == o.state).all(), tag + " MT state"
     # scratch left clean for the next step
     assert int(e.row_count.abs().sum()) == 0
     assert float(e.hot_grad.abs().sum()) == 0.0
+    print(f"\nstep parity {loss}/{opt}/d{d} ({lc.layout_of(d)}) B{B} n{n}{' hot' if hot else ''}"
+          f"{' plan' if plan else ''}: {shares}")
     return e, o
 
 
@@ -193,10 +243,12 @@ def test_mf_step_losses_optimizers(dev, loss, opt):
     run_parity(dev, 300, 200, 64, 128, 5, loss, opt)
 
 
-@pytest.mark.parametrize("d", [8, 16, 32, 50, 64, 100, 128, 200, 256, 1, 7])
+@pytest.mark.parametrize("d", lc.OLD_STEP_DIMS + lc.NEW_STEP_DIMS)
 def test_mf_step_dims(dev, d):
-    run_parity(dev, 200, 150, d, 64, 5, "bpr", "adam")
-    run_parity(dev, 200, 150, d, 64, 3, "pointwise", "adam")
+    """Every dim of mf_layout_common.LAYOUT_DIMS: each scalar layout at the first, an interior and
+    the last dim of its range, the six float4 layouts."""
+    for kw in lc.step_dims_calls(d):
+        run_parity(dev, **kw)
 
 
 @pytest.mark.parametrize("n", [1, 2, 5, 8])
@@ -204,20 +256,24 @@ def test_mf_step_neg_counts(dev, n):
     run_parity(dev, 200, 150, 32, 96, n, "bpr", "adam")
 
 
-@pytest.mark.parametrize("loss", ["pointwise", "bpr"])
-@pytest.mark.parametrize("plan", [False, True])
-def test_mf_step_hot_rows_overflow(dev, loss, plan):
+# the d = 64 cases keep the ids they had before d was a parameter
+@pytest.mark.parametrize("plan,loss,d", [pytest.param(plan, loss, d, id=f"{plan}-{loss}" + (f"-{d}" if d != 64 else ""))
+                                         for d in lc.HOT_DIMS_OLD + lc.HOT_DIMS_NEW
+                                         for loss in ("pointwise", "bpr") for plan in (False, True)])
+def test_mf_step_hot_rows_overflow(dev, loss, plan, d):
     """Rows touched > RG_MF_LIST_CAP times take the overflow accumulators (no plan) or the
-    planned per-block partial rows (positives' item side)."""
-    run_parity(dev, 50, 40, 64, 256, 5, loss, "adam", hot=True, plan=plan)
+    planned per-block partial rows (positives' item side); d = 24 and 160 on the masked scalar
+    layouts <16,2> and <64,3>."""
+    for kw in lc.hot_calls(d, loss, plan):
+        run_parity(dev, **kw)
 
 
-@pytest.mark.parametrize("d", [8, 32, 50, 64, 128, 256])
-@pytest.mark.parametrize("loss", ["pointwise", "bpr", "hinge", "adaptive_hinge"])
+@pytest.mark.parametrize("d", lc.PLAN_DIMS_OLD + lc.PLAN_DIMS_NEW)
+@pytest.mark.parametrize("loss", lc.MF_LOSSES)
 def test_mf_step_plan(dev, d, loss):
     """Item-sorted plan path (per-block partials for the positives' item side)."""
-    run_parity(dev, 300, 200, d, 256, 5, loss, "adam", plan=True, hot=(d == 64))
-    run_parity(dev, 300, 200, d, 256, 5, loss, "sgd", plan=True, hot=(d == 64))
+    for kw in lc.plan_calls(d, loss):
+        run_parity(dev, **kw)
 
 
 def test_mf_step_batch_of_one(dev):
@@ -247,15 +303,43 @@ def test_mf_step_vs_reference_golden(dev, path):
             cmp(e.params()[k], g[f"s{s}_after_{nm}"].reshape(e.params()[k].shape), what=f"{path} {s} {nm}")
 
 
-@pytest.mark.parametrize("loss,hot,d", [("pointwise", False, 64), ("bpr", False, 64), ("hinge", False, 64),
-                                        ("adaptive_hinge", False, 64), ("bpr", True, 64), ("bpr", False, 8),
-                                        ("bpr", False, 50), ("bpr", False, 200), ("pointwise", True, 256),
-                                        ("bpr", True, 128)])
+def grad_ref_and_bound(before, out, pu, pi, loss, n, B):
+    """The oracle's four flat data gradients of a step (``out`` = step(..., return_all=True) from the
+    tables ``before``) and, per element, sum|terms|: the same sums over |dz| and |partner row|."""
+    Uo, Io, ubo, ibo = before
+    u = torch.cat([torch.from_numpy(pu).long(), out["neg_u"]])
+    i = torch.cat([torch.from_numpy(pi).long(), out["neg_i"]])
+    p = torch.cat([out["p_pos"], out["p_neg"]])
+    _, dpp, dpn = omf.loss_and_dp(loss, out["p_pos"], out["p_neg"], n, B)
+    dz = (torch.cat([dpp, dpn]) * (1 - p) * p).abs()
+    bU, bI, bub, bib = omf.dense_grads(Uo.abs(), Io.abs(), ubo, ibo, u, i, dz)
+    ref = [x.double().numpy().reshape(-1) for x in out["grads"]]
+    terms = [x.double().numpy().reshape(-1) for x in (bU, bI, bub, bib)]
+    return ref, terms
+
+
+def check_grads(got, ref, terms, what):
+    """|g - g_ref| <= 1e-5 * sum|terms| + 1e-12 on every element of the four tables; returns the
+    largest |g - g_ref| / bound."""
+    worst = 0.0
+    for k in range(4):
+        tol = 1e-5 * terms[k] + 1e-12
+        err = np.abs(got[k] - ref[k])
+        worst = max(worst, float(np.max(err / tol)))
+        bad = err > tol
+        assert not bad.any(), f"{what} table {k}: {bad.sum()} elements (first {np.flatnonzero(bad)[:8].tolist()}), " \
+                              f"max err {np.max(err):.3e}"
+    return worst
+
+
+@pytest.mark.parametrize("loss,hot,d", lc.GRAD_CASES_OLD + lc.GRAD_CASES_NEW)
 def test_mf_gradients_elementwise(dev, loss, hot, d):
     """The flat data gradient (rg_mf_grads) against the oracle, element by element,
     with a bound that follows each element's condition: |g - g_ref| <= 1e-5 * sum|terms|.
     Teacher-forced: the engine's tables are set to the oracle's before every step, so
-    no earlier step's rounding feeds in."""
+    no earlier step's rounding feeds in.  One dim on every layout of
+    mf_layout_common.LAYOUT_DIMS, <64,3> at its first, last and full row too, and the overflow
+    accumulators (hot) on <16,2> and <64,3>."""
     from recommendation_gans_amd.mf_engine import MFEngine
     U, I, B, n = 300, 200, 128, 5
     tabs, pool_u, pool_i, steps = make_case(U, I, d, B, n, 5000, 3, hot_items=hot)
@@ -264,39 +348,32 @@ def test_mf_gradients_elementwise(dev, loss, hot, d):
                      weight_decay=1e-5, n_neg=n, batch_size=B)
     e = MFEngine(tabs[0], tabs[1], tabs[2].reshape(-1), tabs[3].reshape(-1), pool_u, pool_i, st.copy(), loss=loss,
                  optimizer="adam", lr=1e-2, weight_decay=1e-5, n_neg=n, batch_size=B, device=dev)
+    worst = 0.0
     for s, (pu, pi) in enumerate(steps):
-        Uo, Io, ubo, ibo = [p.clone() for p in o.params]
-        e.set_params(Uo, Io, ubo, ibo)
+        before = [p.clone() for p in o.params]
+        e.set_params(*before)
         out = o.step(pu, pi, return_all=True)
         du, di = torch.from_numpy(pu).to(dev), torch.from_numpy(pi).to(dev)
         g = e.grads(du, di, plan=e.make_plan(di) if s % 2 else None).cpu().double().numpy()
-        u = torch.cat([torch.from_numpy(pu).long(), out["neg_u"]])
-        i = torch.cat([torch.from_numpy(pi).long(), out["neg_i"]])
-        p = torch.cat([out["p_pos"], out["p_neg"]])
-        _, dpp, dpn = omf.loss_and_dp(loss, out["p_pos"], out["p_neg"], n, B)
-        dz = (torch.cat([dpp, dpn]) * (1 - p) * p).abs()
-        bU, bI, bub, bib = omf.dense_grads(Uo.abs(), Io.abs(), ubo, ibo, u, i, dz)
-        ref = [x.double().numpy().reshape(-1) for x in out["grads"]]
-        bound = [x.double().numpy().reshape(-1) for x in (bU, bI, bub, bib)]
+        ref, terms = grad_ref_and_bound(before, out, pu, pi, loss, n, B)
         D = d
         got = [g[:U * D], g[U * D:(U + I) * D], g[(U + I) * D:(U + I) * D + U], g[(U + I) * D + U:(U + I) * (D + 1)]]
-        for k in range(4):
-            tol = 1e-5 * bound[k] + 1e-12
-            bad = np.abs(got[k] - ref[k]) > tol
-            assert not bad.any(), f"step {s} table {k}: {bad.sum()} elements, max err " \
-                                  f"{np.max(np.abs(got[k] - ref[k])):.3e}"
+        worst = max(worst, check_grads(got, ref, terms, f"step {s}"))
         close(g[-1], np.float32(out["loss"]), what="loss slot")
         assert (e.mt_state() == o.state).all()
+    print(f"\ngradients {loss}{' hot' if hot else ''} d{d} ({lc.layout_of(d)}): largest |g - g_ref| / bound {worst:.3f}")
 
 
-@pytest.mark.parametrize("loss", ["pointwise", "bpr"])
-def test_mf_dense_update_path(dev, loss):
+# the d = 64 cases keep the ids they had before d was a parameter
+@pytest.mark.parametrize("loss,d", [pytest.param(loss, d, id=loss + (f"-{d}" if d != 64 else ""))
+                                    for d in (64, 24, 160, 192) for loss in ("pointwise", "bpr")])
+def test_mf_dense_update_path(dev, loss, d):
     """The replicated data-parallel step at world size 1 without a communicator
     (rg_mf_stepper_dp_begin: pairs -> rank-major rg_mf_grads_sharded; identity exchange;
     rg_mf_stepper_dp_end: rg_mf_apply_shard) tracks the oracle over several steps,
-    optimizer state included."""
+    optimizer state included; d = 24 on <16,2>, 160 and the full row 192 on <64,3>."""
     from recommendation_gans_amd.mf_engine import MFEngine
-    U, I, d, B, n = 300, 200, 64, 128, 5
+    U, I, B, n = 300, 200, 128, 5
     tabs, pool_u, pool_i, steps = make_case(U, I, d, B, n, 5000, 4)
     st = orng.py_seed_state(8)
     o = omf.MFOracle(*[t.clone() for t in tabs], pool_u, pool_i, st.copy(), loss=loss, optimizer="adam", lr=1e-2,
@@ -338,7 +415,7 @@ def _ulps(a, b):
     return np.abs(a.numpy().view(np.int32).astype(np.int64) - b.numpy().view(np.int32).astype(np.int64))
 
 
-@pytest.mark.parametrize("d", [64, 50])
+@pytest.mark.parametrize("d", [64, 50, 24, 160])
 @pytest.mark.parametrize("opt", ["adam", "sgd", "rms"])
 def test_optimizer_update_matches_torch(dev, opt, d):
     """Given the same gradient, rg_mf_apply_dense's update is torch.optim's
@@ -397,19 +474,36 @@ def test_optimizer_update_matches_torch(dev, opt, d):
                  f"g {float(grads[k].reshape(-1)[worst])!r}")
 
 
-def test_scores_and_val_loss(dev):
-    e, o = run_parity(dev, 300, 200, 64, 128, 5, "pointwise", "adam")
+def scores_and_val_loss(dev, d):
+    (kw,) = lc.score_val_calls(d)
+    e, o = run_parity(dev, **kw)
     rs = np.random.RandomState(1)
     u, i = rs.randint(0, 300, 1000), rs.randint(0, 200, 1000)
     got = e.scores(torch.from_numpy(u), torch.from_numpy(i))
     ref = omf.scores(*o.params, torch.from_numpy(u), torch.from_numpy(i))
-    close(got, ref, what="scores")
+    share = close(got, ref, what="scores")
+    # and against the float64 product of the engine's own tables (the oracle's differ by a step's rounding)
+    ref64 = omf.scores(*[p.double().cpu().reshape(r.shape) for p, r in zip(e.params(), o.params)],
+                       torch.from_numpy(u), torch.from_numpy(i))
+    share = max(share, close(got, ref64, what="scores against float64"))
     vu, vi = rs.randint(0, 300, 100), rs.randint(0, 200, 100)
     got = e.val_loss(torch.from_numpy(vu).to(dev), torch.from_numpy(vi).to(dev))
     ref = omf.val_loss(o, vu, vi)
     torch.cuda.synchronize()
-    close(got[0], np.float32(ref), what="val loss")
+    share_v = close(got[0], np.float32(ref), what="val loss")
     assert (e.mt_state() == o.state).all()
+    print(f"scores / val loss d{d} ({lc.layout_of(d)}): share of the 1e-5 allowance {share:.3f} / {share_v:.3f}")
+
+
+def test_scores_and_val_loss(dev):
+    scores_and_val_loss(dev, 64)
+
+
+@pytest.mark.parametrize("d", lc.SCORE_VAL_DIMS_NEW)
+def test_scores_and_val_loss_dims(dev, d):
+    """rg_mf_scores and the validation loss on every layout: the scalar layouts at an interior dim,
+    <16,2> at its first dim, <64,3> at its first, last and full row, and the other float4 sizes."""
+    scores_and_val_loss(dev, d)
 
 
 def test_large_full_size_properties(dev):

@@ -49,7 +49,9 @@ OPT_CASES = [  # E, M, loss, optimizer, n_neg, planned
     (8, 5, "pointwise", "rms", 5, False), (8, 5, "bpr", "rms", 4, True),
     (32, 20, "pointwise", "sgd", 5, False), (32, 20, "bpr", "sgd", 4, True),
     (32, 20, "pointwise", "rms", 5, True), (32, 20, "hinge", "rms", 4, False),
-    (32, 0, "pointwise", "adam", 5, True)]
+    (32, 0, "pointwise", "adam", 5, True),
+    # the GMF half (dispatched on M) on the scalar layouts <16,2>, <64,2> and the first dim of <64,2>
+    (16, 24, "bpr", "adam", 4, False), (16, 100, "pointwise", "adam", 5, True), (8, 65, "bpr", "adam", 4, True)]
 
 
 @pytest.mark.parametrize("E,M,loss,optimizer,n,planned", OPT_CASES)
@@ -113,7 +115,7 @@ def test_ncf_partial_last_batch(E, loss, n_pos, planned):
 
 # ---------------------------------------------------------------------------- validation loss
 @pytest.mark.parametrize("loss", LOSSES)
-@pytest.mark.parametrize("M", [0, 5, 50])
+@pytest.mark.parametrize("M", [0, 5, 50, 24, 100])
 @pytest.mark.parametrize("E", [8, 16, 32])
 def test_ncf_tile_and_neumf_validation_loss(E, M, loss):
     """run_val_iteration through the tile kernel's loss-only phase (adaptive hinge: its scores

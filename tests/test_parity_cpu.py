@@ -1,7 +1,10 @@
 """oracle.mf.elementwise_parity: the elementwise rule behind the full-size GPU tests."""
+import numpy as np
+import pytest
 import torch
 
 from oracle import mf as omf
+from tests import mf_layout_common as lc
 
 
 def test_elementwise_catches_what_the_norm_hides():
@@ -228,3 +231,65 @@ def test_kink_envelope_covers_the_kink_flip_sample():
         fail_env += s1["n_fail"]
         fail_band += s2["n_fail"]
     assert fail_env == 0 and fail_band > 0, (fail_env, fail_band)
+
+
+# ---------------------------------------------------------------- the layout cases of test_mf_gpu.py
+# tests/mf_layout_common.py lists every run_parity call and every gradient case that the layout
+# tests add on the GPU.  Here the reference alone goes through them first: over the same make_case
+# inputs, MFOracle(order_seed=1) -- the same fp32 step summing its gradients in another order, as
+# the GPU does -- must pass the very criterion the GPU result is held to (test_mf_gpu.check_step:
+# close on the loss, close_adam with small= on the biases, close under SGD; check_grads: the
+# per-element bound 1e-5 * sum|terms| + 1e-12), against the fp32 oracle and the float64 oracle.  A
+# case that another summation order of the reference itself could not pass would test the order,
+# not the kernel.  Every step case passes with its seed and its pairing of loss and dim as first
+# written.  One gradient case was re-paired: d = 1 runs pointwise instead of bpr, because under bpr
+# the fp32 oracle's own gradient sits 1.25 times the bound from the float64 gradient on one element
+# (a saturated sigmoid on one-column N(0, 1) tables); the tolerance is unchanged.
+def _case_id(c):
+    return "-".join(f"{k}{v}" for k, v in c.items() if k not in ("U", "I"))
+
+
+@pytest.mark.parametrize("parity_call", lc.new_parity_calls(), ids=_case_id)
+def test_layout_step_cases_pass_on_the_reference_alone(parity_call):
+    from tests import test_mf_gpu as tm
+    kw = dict(parity_call)
+    opt = kw["opt"]
+    _, _, _, steps, _, (o, alt), o64 = tm.make_oracles(**kw, order_seeds=(None, 1))
+    shares = tm.Shares()
+    for s, (pu, pi) in enumerate(steps):
+        ref_loss = o.step(pu, pi)
+        alt_loss = alt.step(pu, pi)
+        o64.step(pu, pi)
+        tm.check_step(f"{_case_id(kw)} step {s}", opt, np.float32(alt_loss), alt.params,
+                      [st[0] for st in alt.opt.state], [st[1] for st in alt.opt.state], o, o64, ref_loss, shares)
+        assert (alt.state == o.state).all() and (o64.state == o.state).all()
+    print(f"\nreference alone {_case_id(kw)}: {shares}")
+
+
+@pytest.mark.parametrize("grad_case", lc.GRAD_CASES_NEW, ids=lambda c: "-".join(str(x) for x in c))
+def test_layout_gradient_cases_pass_on_the_reference_alone(grad_case):
+    """test_mf_gradients_elementwise's new cases, teacher-forced as there: the reordered fp32
+    gradient and the float64 gradient against the fp32 oracle's, within the per-element bound."""
+    from oracle import rng as orng
+    from tests import test_mf_gpu as tm
+    loss, hot, d = grad_case
+    U, I, B, n = 300, 200, 128, 5
+    tabs, pool_u, pool_i, steps = tm.make_case(U, I, d, B, n, 5000, 3, hot_items=hot)
+    st = orng.py_seed_state(7)
+    kw = dict(loss=loss, optimizer="adam", lr=1e-2, weight_decay=1e-5, n_neg=n, batch_size=B)
+    o = omf.MFOracle(*[t.clone() for t in tabs], pool_u, pool_i, st.copy(), **kw)
+    alt = omf.MFOracle(*[t.clone() for t in tabs], pool_u, pool_i, st.copy(), order_seed=1, **kw)
+    o64 = omf.MFOracle(*[t.clone().double() for t in tabs], pool_u, pool_i, st.copy(), **kw)
+    worst = [0.0, 0.0]
+    for s, (pu, pi) in enumerate(steps):
+        before = [p.clone() for p in o.params]
+        for other in (alt, o64):                       # teacher-forced from the fp32 oracle's tables
+            for p, b in zip(other.params, before):
+                p.copy_(b)
+        out = o.step(pu, pi, return_all=True)
+        ref, terms = tm.grad_ref_and_bound(before, out, pu, pi, loss, n, B)
+        for j, other in enumerate((alt, o64)):
+            got = [x.double().numpy().reshape(-1) for x in other.step(pu, pi, return_all=True)["grads"]]
+            worst[j] = max(worst[j], tm.check_grads(got, ref, terms, f"{grad_case} step {s} oracle {j}"))
+    print(f"\nreference alone, gradients {grad_case}: largest |g - g_ref| / bound, another fp32 order "
+          f"{worst[0]:.3f}, float64 {worst[1]:.3f}")

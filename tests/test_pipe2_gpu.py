@@ -78,7 +78,8 @@ def _same(a, b, what=""):
 
 @pytest.mark.parametrize("loss,d,ahead", [("bpr", 64, True), ("pointwise", 64, True), ("hinge", 64, True),
                                           ("bpr", 32, True), ("bpr", 128, True), ("bpr", 64, False),
-                                          ("pointwise", 50, True)])
+                                          ("pointwise", 50, True),
+                                          ("bpr", 24, True), ("pointwise", 160, True)])   # <16,2>, <64,3>
 def test_pipe2_step_is_bit_identical(loss, d, ahead):
     U, I, B, n, steps = 3000, 400, 1024, 5, 7
     ref, pipe = _engine(False, loss, d, U, I, B, n), _engine(True, loss, d, U, I, B, n)
