@@ -20,8 +20,9 @@ tests/golden records them with forward hooks), scaled by 1 / (1 - 0.5) = 2.
 Pinned by tests/golden/mlp_*.npz and neumf_*.npz (made by importing the reference).
 
 Samples of the fp32 rounding noise (tests/parity_report.py's elementwise band): ``order_seed``
-runs a step with the examples, the input features and every hidden layer's units in seeded
-orders (every batch sum and every product's inner sum re-ordered, forward and backward);
+runs a step with the examples (pointwise only: the pairwise losses tie a negative to its column),
+the input features and every hidden layer's units in seeded orders (every batch sum and every
+product's inner sum re-ordered, forward and backward);
 ``kink_flip`` decides every LeakyReLU (mlp.py:36, neuMF.py:48) whose pre-activation lies within
 fp32 rounding of the kink the other way from its exact value -- the activation decision a
 different fp32 order of the forward dot product can take (see ``kink_band``).
@@ -190,6 +191,146 @@ def kink_envelope(P, u, i, masks, cache, c, env, n_emb):
     return count
 
 
+def grad_terms(P, u, i, masks, cache, dp):
+    """The absolute backward (run it in float64): the pass of ``backward`` / ``neumf_backward`` with
+    |dz| at the output, |W|, |a_prev|, the masks times DROP_SCALE and the LeakyReLU slopes, so every
+    product and every sum of the backward pass adds the absolute values of its terms.  Returns, in
+    parameter order and per element, the sum over the examples of the absolute value of every term
+    of that element's gradient sum -- the scale of the rounding error any fp32 order of the same
+    sums makes (the analogue of tests/test_mf_gpu.py grad_ref_and_bound).  NeuMF: the GMF rows
+    take |dz| * |affine_output.weight[8 + c]| * |partner row|."""
+    p = cache["p"]
+    dz = (dp * (1 - p) * p).abs()
+    lin = [(W.abs(), b) for W, b in P.linears()]
+    hid = lin[:-1]
+    neumf = isinstance(P, NeuMFParams)
+    Wo = lin[-1][0]
+    vin = cache["v"].abs() if neumf else cache["a"][len(hid)].abs()
+    grads_lin = [(dz.t().mm(vin), dz.sum(0))]
+    dv = dz.mm(Wo)
+    T = hid[-1][0].shape[0] if hid else Wo.shape[1]
+    da = dv[:, :T]
+    for k in range(len(hid) - 1, -1, -1):
+        da = da * (masks[k].to(dz.dtype) * DROP_SCALE)
+        dzk = torch.where(cache["pos"][k], da, da * LRELU)
+        grads_lin.append((dzk.t().mm(cache["a"][k].abs()), dzk.sum(0)))
+        da = dzk.mm(hid[k][0])
+    grads_lin.reverse()
+    Ue, Ie = P.emb()
+    E = Ue.shape[1]
+    out = [torch.zeros_like(Ue).index_add_(0, u, da[:, :E]), torch.zeros_like(Ie).index_add_(0, i, da[:, E:])]
+    if neumf:
+        Um, Im = P.emb_mf()
+        dg = dv[:, T:]
+        out += [torch.zeros_like(Um).index_add_(0, u, dg * cache["gmf_i"].abs()),
+                torch.zeros_like(Im).index_add_(0, i, dg * cache["gmf_u"].abs())]
+    for dW, db in grads_lin:
+        out += [dW, db]
+    return out
+
+
+def _dot_var(a, W, b):
+    """Variance, in units of u^2, of an fp32 dot product a @ W.T + b summed in some order: K
+    roundings of partial sums whose size is that of a random walk over the terms, so
+    K * (sum of the squared terms) -- kink_band's u sqrt(K) S with the terms added in quadrature
+    instead of in absolute value (S^2 is the worst case, every term of one sign)."""
+    return (W.shape[1] + 1) * ((a * a).mm((W * W).t()) + b * b)
+
+
+def forward_error(P, masks, cache):
+    """First-order estimate (run it in float64) of how far an fp32 forward pass in another
+    summation order lands from this one, as variances in units of u^2: per layer input ``va`` of
+    the activations (va[0] = 0: the gathered rows are exact), ``vv`` of the output Linear's inputs
+    and ``vz`` of the output logit.  A pre-activation takes its own rounding (``_dot_var``) and its
+    inputs' variances through W^2 -- independent roundings add in quadrature, which is what the
+    signed weights do to them; through |W| they would compound as if every error of every layer
+    had the worst sign (a factor of about sqrt(width) per layer, 300 times the fp32 oracle's own
+    distance at E = 64).  LeakyReLU and dropout scale by the unit's slope and mask * DROP_SCALE
+    (decisions within the band are the kink envelope's business, not this estimate's)."""
+    lin = P.linears()
+    neumf = isinstance(P, NeuMFParams)
+    va = [torch.zeros_like(cache["a"][0])]
+    for k, (W, b) in enumerate(lin[:-1]):
+        vz = va[k].mm((W * W).t()) + _dot_var(cache["a"][k], W, b)
+        f = torch.where(cache["pos"][k], 1.0, LRELU).to(vz.dtype) * (masks[k].to(vz.dtype) * DROP_SCALE)
+        va.append(vz * f * f)
+    W, b = lin[-1]
+    if neumf:
+        v = cache["v"]
+        vv = torch.cat([va[-1], (cache["gmf_u"] * cache["gmf_i"]) ** 2], dim=-1)
+    else:
+        v, vv = cache["a"][len(lin) - 1], va[-1]
+    return va, vv, vv.mm((W * W).t()) + _dot_var(v, W, b)
+
+
+def score_error(cache, vz):
+    """Standard error (units of u) of the fp32 score p = sigmoid(z): p (1 - p) sz and the rounding of
+    p itself, in quadrature."""
+    p = cache["p"]
+    return ((p * (1 - p)) ** 2 * vz + p * p).sqrt()
+
+
+def dp_error(kind, p_pos, p_neg, sp_pos, sp_neg, n, batch_size):
+    """Standard error of dL/dp (omf.loss_and_dp) given the scores' sp: pointwise dp = -1 / (p Bp)
+    and 1 / ((1 - p) N) move by sp / (p^2 Bp) and sp / ((1 - p)^2 N); bpr's -g (1 - s) s,
+    s = sigmoid(pos - neg), has |d/dx| <= 0.1 and sees both scores of its pair (a positive's dp sums
+    its n pairs, whose negatives err independently); the hinges' dp is piecewise constant (their
+    kinks are preconditions of the cases)."""
+    Bp = p_pos.shape[0]
+    if kind == "pointwise":
+        return sp_pos / (p_pos ** 2 * Bp), sp_neg / ((1 - p_neg) ** 2 * p_neg.shape[0])
+    if kind == "bpr":
+        g = 0.1 / (n * Bp)
+        vn = torch.zeros(n, batch_size, dtype=p_pos.dtype)
+        sn = sp_neg.view(n, batch_size)[:, :Bp]
+        vn[:, :Bp] = g * g * (sn * sn + (sp_pos * sp_pos)[None, :])
+        vp = g * g * ((sn * sn).sum(0) + (n * sp_pos) ** 2)
+        return vp.sqrt(), vn.reshape(-1).sqrt()
+    return torch.zeros_like(p_pos), torch.zeros_like(p_neg)
+
+
+def forward_error_terms(P, u, i, masks, cache, dp, sdp, va, vv, sp):
+    """The variance (units of u^2, float64) that the forward pass's rounding gives every element of
+    the data gradient, to first order: the backward pass of ``grad_terms`` carrying, beside dz,
+    the variance vdz of every dz.  At the output dz = dp (1 - p) p has the standard error
+    |dp| sp + (1 - p) p sdp (sp from ``score_error``, which carries fp32's loss of (1 - p) near 1;
+    sdp from ``dp_error``; both come from the same score, so they add coherently); a weight
+    gradient sum of dz * a gains vdz a^2 + dz^2 va per example; the rest of the backward is linear
+    in dz, and its variances go through W^2 and the squared slopes and masks (see
+    ``forward_error``).  Examples err independently, so their variances add."""
+    p = cache["p"]
+    dz = dp * (1 - p) * p
+    vdz = (dp.abs() * sp + (1 - p) * p * sdp) ** 2
+    lin = P.linears()
+    hid = lin[:-1]
+    neumf = isinstance(P, NeuMFParams)
+    Wo = lin[-1][0]
+    vin = cache["v"] if neumf else cache["a"][len(hid)]
+    grads_lin = [(vdz.t().mm(vin * vin) + (dz * dz).t().mm(vv), vdz.sum(0))]
+    dv, vdv = dz.mm(Wo), vdz.mm(Wo * Wo)
+    T = hid[-1][0].shape[0] if hid else Wo.shape[1]
+    da, vda = dv[:, :T], vdv[:, :T]
+    for k in range(len(hid) - 1, -1, -1):
+        f = masks[k].to(dz.dtype) * DROP_SCALE * torch.where(cache["pos"][k], 1.0, LRELU).to(dz.dtype)
+        dzk, vdzk = da * f, vda * f * f
+        ak = cache["a"][k]
+        grads_lin.append((vdzk.t().mm(ak * ak) + (dzk * dzk).t().mm(va[k]), vdzk.sum(0)))
+        W = hid[k][0]
+        da, vda = dzk.mm(W), vdzk.mm(W * W)
+    grads_lin.reverse()
+    Ue, Ie = P.emb()
+    E = Ue.shape[1]
+    out = [torch.zeros_like(Ue).index_add_(0, u, vda[:, :E]), torch.zeros_like(Ie).index_add_(0, i, vda[:, E:])]
+    if neumf:
+        Um, Im = P.emb_mf()
+        vdg = vdv[:, T:]
+        out += [torch.zeros_like(Um).index_add_(0, u, vdg * cache["gmf_i"] ** 2),
+                torch.zeros_like(Im).index_add_(0, i, vdg * cache["gmf_u"] ** 2)]
+    for dW, db in grads_lin:
+        out += [dW, db]
+    return out
+
+
 class NCFOracle:
     """One run_train_iteration (implicit.py:347-364) of the NCF MLP per ``step``."""
 
@@ -197,13 +338,17 @@ class NCFOracle:
 
     def __init__(self, tensors, names, pool_u, pool_i, mt_state, loss="pointwise", lr=1e-2, weight_decay=1e-5,
                  n_neg=5, batch_size=256, betas=(0.5, 0.999), order_seed=None, kink_flip=None, kink_env=None,
-                 optimizer="adam", eps=1e-8, alpha=0.99):
+                 optimizer="adam", eps=1e-8, alpha=0.99, grad_bounds=False):
         self.P = MLPParams(tensors, names)
-        # order_seed (pointwise, test infrastructure): run the step over the examples, the input
-        # features and every hidden layer's units in seeded orders -- the same arithmetic summed
-        # in other fp32 orders (batch sums and every product's inner sum), a further sample of
-        # the rounding noise for tests/parity_report.py's elementwise band
-        assert order_seed is None or loss == "pointwise"
+        # grad_bounds (float64, test infrastructure): step(return_all=True) also returns ``terms``
+        # (grad_terms) and ``fwd`` (forward_error_terms as one standard error per element)
+        self.grad_bounds = grad_bounds
+        # order_seed (test infrastructure): run the step over the input features and every hidden
+        # layer's units in seeded orders, and under the pointwise loss the examples too (the other
+        # losses pair a negative with its column, so their examples keep their places) -- the same
+        # arithmetic summed in other fp32 orders (every product's inner sum; pointwise: the batch
+        # sums), a further sample of the rounding noise for tests/parity_report.py's elementwise
+        # band and tests/ncf_grad_common.py's calibration
         self.order = None if order_seed is None else torch.Generator().manual_seed(order_seed)
         # kink_flip (test infrastructure): c of kink_band -- every LeakyReLU decision within
         # rounding of the kink goes the other way from the exact sign of this run's own state; the
@@ -217,6 +362,9 @@ class NCFOracle:
         assert kink_env is None or order_seed is None
         self.kink_env = kink_env
         self.kink_noise, self.kink_count = None, []
+        # the same envelope before the optimizer: per parameter, how far those flips move the
+        # step's data gradient (tests/ncf_grad_common.py's K)
+        self.kink_grad_env = None
         self.loss_kind = loss
         self.n, self.batch_size = n_neg, batch_size
         # optimizer: "adam", "sgd" or "rms" (spotlight/optimizers.py:4-22 through omf.Optim)
@@ -233,7 +381,7 @@ class NCFOracle:
         return idx, self.pool_u[t], self.pool_i[t]
 
     def _permuted(self, u, i, masks):
-        if self.order is None:
+        if self.order is None or self.loss_kind != "pointwise":
             return u, i, masks
         pr = torch.randperm(len(u), generator=self.order)
         return u[pr], i[pr], [m[pr] for m in masks]
@@ -282,6 +430,7 @@ class NCFOracle:
         env = [torch.zeros(t.shape, dtype=torch.float64) for t in self.P.t]
         n = sum(kink_envelope(P, uu, ii, mm, cc, self.kink_env, env, self.N_EMB) for uu, ii, mm, cc in (pos, neg))
         self.kink_count.append(n)
+        self.kink_grad_env = env
         dstate = [(torch.zeros_like(e), torch.zeros_like(e)) for e in env]
         self.kink_noise = self.opt.sensitivity(self.P.t, grads, env, dstate)
 
@@ -303,9 +452,25 @@ class NCFOracle:
         g2 = self._bwd(P, nu, ni, masks_neg, c_neg, dpn.reshape(-1, 1), xperm)
         grads = gback([a + b for a, b in zip(g1, g2)])
         self._envelope(P, (u, i, masks_pos, c_pos), (nu, ni, masks_neg, c_neg), grads)
+        terms = fwd = None
+        if return_all and self.grad_bounds:
+            assert self.order is None and p_pos.dtype == torch.float64
+            terms = [a + b for a, b in zip(grad_terms(P, u, i, masks_pos, c_pos, dpp.reshape(-1, 1)),
+                                           grad_terms(P, nu, ni, masks_neg, c_neg, dpn.reshape(-1, 1)))]
+            va_p, vv_p, vz_p = forward_error(P, masks_pos, c_pos)
+            va_n, vv_n, vz_n = forward_error(P, masks_neg, c_neg)
+            sp_p, sp_n = score_error(c_pos, vz_p), score_error(c_neg, vz_n)
+            sdp_p, sdp_n = dp_error(kind, p_pos.reshape(-1), p_neg.reshape(-1), sp_p.reshape(-1), sp_n.reshape(-1),
+                                    self.n, self.batch_size)
+            var = [a + b for a, b in zip(
+                forward_error_terms(P, u, i, masks_pos, c_pos, dpp.reshape(-1, 1), sdp_p.reshape(-1, 1), va_p, vv_p, sp_p),
+                forward_error_terms(P, nu, ni, masks_neg, c_neg, dpn.reshape(-1, 1), sdp_n.reshape(-1, 1), va_n, vv_n,
+                                    sp_n))]
+            fwd = [U32 * v.sqrt() for v in var]      # one standard error of the forward pass's rounding
         self.opt.step(self.P.t, grads)
         if return_all:
-            return dict(loss=float(loss), p_pos=p_pos, p_neg=p_neg, neg_idx=idx, neg_u=nu, neg_i=ni, grads=grads)
+            return dict(loss=float(loss), p_pos=p_pos, p_neg=p_neg, neg_idx=idx, neg_u=nu, neg_i=ni, grads=grads,
+                        terms=terms, fwd=fwd)
         return float(loss)
 
 

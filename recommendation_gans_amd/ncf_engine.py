@@ -113,6 +113,7 @@ class NCFEngine:
         M = self.M
         # data parallel: [embedding rows (U+I)(E+1)+1 | GMF rows (U+I)(M+1)+1 | MLP P+1], one all-reduce
         self.dp_flat = None
+        self._grad_bufs = None        # grads(): (emb, gmf, mlp), allocated on its first call
         if self.world > 1:
             ne, nm = rows * (E + 1) + 1, (rows * (M + 1) + 1) if self.neumf else 0
             self.dp_flat = torch.zeros(ne + nm + self.P + 1, **f32)
@@ -396,6 +397,62 @@ class NCFEngine:
         self._prefetch_tail(next_step, stream)
         check(self.lib.rg_mf_stepper_advance(self._stepper, 0, 1), "rg_mf_stepper_advance")
         return out
+
+    def grads(self, pos_u, pos_i, global_pos=None, plan=None, masks=None):
+        """The step's data gradients without an update (single rank; the counterpart of
+        MFEngine.grads): the forward / loss / backward of ``train_step`` on the same draw and the
+        same dropout, then the data-parallel path's pulls (rg_ncf_mlp_grad, rg_ncf_grads) instead
+        of the optimizer.  Returns device tensors ``(emb, gmf, mlp)`` in the layouts of
+        include/rg_hip.h:
+
+        * ``emb`` [(U + I) * E + (U + I) + 1]: the MLP tables' rows (users, then items), then one
+          slot per row, then an unused 0;
+        * ``gmf`` (NeuMF; None otherwise) [(U + I) * M + (U + I) + 1]: the GMF tables' likewise;
+        * ``mlp`` [P + 1]: the flat MLP gradient in named_parameters() order, then the loss.
+
+        The ``nr`` slots after the rows of ``[nr*D | nr | 0]`` are the MF path's bias gradients.
+        The NCF tables have no bias (has_bias = false), and the pair kernel stores every list
+        entry with the weight 1.0 beside its contribution row (rg_ncf.hip store_entry), so the
+        slot is the sum of those weights: the number of the row's list entries this step,
+        min(examples that claimed a slot of the row, RG_MF_LIST_CAP) -- every valid example for a
+        user, every valid example but the planned positives for an item -- and 0 for an untouched
+        row; the same in ``emb`` and ``gmf``.
+
+        Afterwards the per-row counts and the overflow accumulators are zero, the MT state has
+        moved past the step's draw and the step is counted (the dropout seed and the optimizer's
+        step number move on): a following ``train_step`` behaves as if this had been a step with
+        lr = 0 whose optimizer state was left alone."""
+        if self.world != 1:
+            raise RuntimeError("NCFEngine.grads is single-rank; a data-parallel step exchanges its own gradients")
+        if self._broken:
+            raise RuntimeError("NCFEngine unusable: " + self._broken)
+        if self._grad_bufs is None:
+            rows, f32 = self.U + self.I, dict(dtype=torch.float32, device=self.device)
+            self._grad_bufs = (torch.zeros(rows * (self.E + 1) + 1, **f32),
+                               torch.zeros(rows * (self.M + 1) + 1, **f32) if self.neumf else None,
+                               torch.zeros(self.P + 1, **f32))
+        emb, gmf, mlp = self._grad_bufs
+        n_pos = int(pos_u.numel())
+        global_pos = n_pos if global_pos is None else int(global_pos)
+        x = self._step_in_of(pos_u, pos_i, global_pos, plan)
+        stream = _lib.stream_handle()
+        batch, work = _lib.MFBatch(), _lib.MFWork()
+        ref = ctypes.byref
+        check(self.lib.rg_mf_stepper_acquire(self._stepper, stream, ref(x), ref(batch), ref(work)),
+              "rg_mf_stepper_acquire")
+        self.t += 1
+        nw = self._work(masks, True)
+        self._forward_backward(batch, work, nw, stream)
+        check(self.lib.rg_mf_stepper_release(self._stepper, stream), "rg_mf_stepper_release")
+        parts = self.adapt_partials if self.loss == "adaptive_hinge" else self.partials
+        check(self.lib.rg_ncf_mlp_grad(stream, ref(self._model), ref(nw), self.blocks, ptr(parts),
+                                       ref(self._loss(global_pos, self.loss_out)), ptr(mlp)), "rg_ncf_mlp_grad")
+        if self.neumf:
+            check(self.lib.rg_ncf_grads(stream, ref(self._model), ref(work), ref(nw), ptr(gmf), 0, -1, 1),
+                  "rg_ncf_grads(gmf)")
+        check(self.lib.rg_ncf_grads(stream, ref(self._model), ref(work), ref(nw), ptr(emb), 0, -1, 0), "rg_ncf_grads")
+        check(self.lib.rg_mf_stepper_advance(self._stepper, 0, 1), "rg_mf_stepper_advance")
+        return emb, gmf, mlp
 
     def _step_in(self, pos_u, pos_i, global_pos):
         n_pos = int(pos_u.numel())

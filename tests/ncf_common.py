@@ -1,6 +1,8 @@
 """Shared pieces of the NCF / NeuMF training-step tests (test_ncf_matrix_gpu.py,
 test_ncf_dropout_gpu.py, test_ncf_dropout_cpu.py, test_ncf_controls_cpu.py).  No test lives
-here and nothing here needs a GPU until ``run_parity`` builds an engine.
+here and nothing here needs a GPU until ``run_parity`` builds an engine.  The elementwise
+gradient rule and its cases (test_ncf_grads_cpu.py, test_ncf_grads_gpu.py) are in
+tests/ncf_grad_common.py, which builds on the pieces below.
 
 * ``make_params``: an NCF tower (M = 0) or a NeuMF model in named_parameters() order, initialised
   as the reference initialises them (N(0, 1) embeddings, Xavier-uniform weights, bias 0.01).
