@@ -25,6 +25,8 @@
 // lane reduction is the same butterfly in every group; the wave loops to its longest row and masks
 // with selects.  So a row's bits depend on its own list, values, start and
 // G alone -- not on its place in the call, the number of rows or the other rows.  No atomics.
+// The layout dispatch (dispatch_rows, capped at dim 128), the dots (row_dot) and wave_max64 are the
+// row-group helpers of rg_common.h; the launch, with its dynamic LDS and strided grids, is its own.
 //
 // rg_als_gram: blocks of kGramRows rows each write a [dim][dim] partial (an 8 x 8 register tile per
 // thread, the rows staged through LDS kGramTile at a time: a tile's rows summed in ascending order,
@@ -63,26 +65,6 @@ struct AlsArgs {
     float *X, *loss_out;
 };
 
-// wave-uniform maximum of a non-negative 64-bit count
-__device__ __forceinline__ int64_t wave_max64(int64_t x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const int64_t y = __shfl_xor(x, o);
-        x = y > x ? y : x;
-    }
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)x);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)x >> 32));
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
-template <class L>
-__device__ __forceinline__ float group_dot(const float (&a)[L::EPL], const float (&b)[L::EPL]) {
-    float d = 0.0f;
-#pragma unroll
-    for (int e = 0; e < L::EPL; ++e) d = fmaf(a[e], b[e], d);
-    return group_sum<L::LPU>(d);
-}
-
 // One pass over entries [lo, lo + cnt) of the list, the wave looping to max_cnt (wave-uniform):
 //   MODE 0: acc = sum (c_i - 1) (y_i . v) y_i and bs = sum c_i y_i
 //   MODE 1: acc alone
@@ -117,7 +99,7 @@ __device__ __forceinline__ void gather_pass(const AlsArgs &a, int sub, int64_t l
         for (int u = 0; u < kKB; ++u) L::load(y[u], a.Y, id[u], D, sub);
 #pragma unroll
         for (int u = 0; u < kKB; ++u) {
-            const float s = group_dot<L>(y[u], v);
+            const float s = row_dot<L>(y[u], v);
             const float c = 1.0f + c1[u];
             if (MODE != 2) {
                 const float t = c1[u] * s;
@@ -243,7 +225,7 @@ __device__ __forceinline__ void als_row(const AlsArgs &a, const float *Gs, float
             r[e] = bs[e] - (ap[e] + acc[e]);
             p[e] = r[e];
         }
-        float rs = group_dot<L>(r, r);
+        float rs = row_dot<L>(r, r);
         bool go = act;
         for (int it = 0; it < a.steps; ++it) {
             go = go && rs != 0.0f;
@@ -253,7 +235,7 @@ __device__ __forceinline__ void als_row(const AlsArgs &a, const float *Gs, float
             g_times<L>(Gs, ps, D, sub, p, ap);
 #pragma unroll
             for (int e = 0; e < EPL; ++e) ap[e] += acc[e];
-            const float pap = group_dot<L>(p, ap);
+            const float pap = row_dot<L>(p, ap);
             go = go && pap > 0.0f;
             const float al = rs / pap;
 #pragma unroll
@@ -261,7 +243,7 @@ __device__ __forceinline__ void als_row(const AlsArgs &a, const float *Gs, float
                 x[e] = go ? fmaf(al, p[e], x[e]) : x[e];
                 r[e] = go ? fmaf(-al, ap[e], r[e]) : r[e];
             }
-            const float rn = group_dot<L>(r, r);
+            const float rn = row_dot<L>(r, r);
             const float beta = rn / rs;
 #pragma unroll
             for (int e = 0; e < EPL; ++e) p[e] = go ? fmaf(beta, p[e], r[e]) : p[e];
@@ -274,7 +256,7 @@ __device__ __forceinline__ void als_row(const AlsArgs &a, const float *Gs, float
         gather_pass<L, 2>(a, sub, lo, cnt, max_cnt, x, acc, bs, ls);
         if (LONG) ls = reduce_scalar<NG>(red_s, gid, sub, ls);
         g_times<L>(Gs, ps, D, sub, x, ap);
-        const float q = group_dot<L>(x, ap);
+        const float q = row_dot<L>(x, ap);
         if (act && sub == 0 && (!LONG || gid == 0)) a.loss_out[row] = q + ls;
     }
 }
@@ -348,17 +330,6 @@ constexpr size_t short_lds(int D) {
 template <class L>
 constexpr size_t long_lds(int D) {
     return (size_t)round4(D * D) + (size_t)3 * kLongWaves * kWave * L::EPL + (size_t)kLongWaves * L::UPW;
-}
-
-// the layout of `dim` <= 128: the pair kernel's (dispatch_dim) when the tables take 16-byte loads,
-// else the scalar-load layouts of the same lane counts
-template <typename F>
-int dispatch_als(int dim, bool aligned, F &&f) {
-    if (aligned && (dim == 8 || dim == 16 || dim == 32 || dim == 64 || dim == 128)) return dispatch_dim(dim, f);
-    if (dim <= 16) return f.template operator()<RowLayout<16, 1, false>>();
-    if (dim <= 32) return f.template operator()<RowLayout<16, 2, false>>();
-    if (dim <= 64) return f.template operator()<RowLayout<16, 4, false>>();
-    return f.template operator()<RowLayout<64, 2, false>>();
 }
 
 struct AlsLaunch {
@@ -504,5 +475,6 @@ extern "C" int rg_als_solve_rows(void *stream, const float *other_table, const f
     if (!row_idx) return fail_arg("rg_als_solve_rows: row_idx is null");
     const AlsArgs a{other_table, G, dim, row_ptr, row_idx, row_val, alpha, rows, n_rows, cg_steps, x_inout, loss_out};
     const bool aligned = (((uintptr_t)other_table | (uintptr_t)x_inout) & 15u) == 0;
-    return dispatch_als(dim, aligned, AlsLaunch{a, (hipStream_t)stream});
+    // the layouts of dim <= kMaxDim alone: none of the wider ones is built for these kernels
+    return dispatch_rows<kMaxDim>(dim, aligned, AlsLaunch{a, (hipStream_t)stream});
 }

@@ -7,7 +7,8 @@
 // rg_mf_score_lists: a list is owned by one group of L::LPU lanes (the pair kernel's row layout,
 // rg_common.h, as in rg_mf_fold.hip), 64 / LPU lists per wave, one wave per workgroup.  The user's
 // row and bias stay in registers while the list is walked kIF entries at a time (kIF gathered item
-// rows in flight per group); a score is the lane's fmaf chain over its elements in ascending order,
+// rows in flight per group); a score (row_score, rg_common.h, with the other row-group helpers
+// used here) is the lane's fmaf chain over its elements in ascending order,
 // the group's butterfly (group_sum), then (dot + b) + c and the sigmoid -- one fixed order that
 // depends on dim and the tables' alignment alone, so a (user, item) pair is the same bits at any
 // position of any list.  The wave loops to its longest list; the shorter ones are masked with
@@ -43,18 +44,6 @@ struct ScoreListArgs {
     float *out;
 };
 
-// wave-uniform maximum of a non-negative 64-bit count
-__device__ __forceinline__ int64_t wave_max64(int64_t x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const int64_t y = __shfl_xor(x, o);
-        x = y > x ? y : x;
-    }
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)x);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)x >> 32));
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
 // dim % 4 == 0 off the pair kernel's sizes, 16-byte aligned tables: lane `sub` of the row's LPU
 // owns the float4 at floats [4 sub, 4 sub + 4) when that lies inside the row, zeros otherwise
 template <int LPU_>
@@ -73,15 +62,6 @@ struct VecLayout {
         for (int e = 0; e < EPL; ++e) v[e] = 0.0f;
     }
 };
-
-template <class L>
-__device__ __forceinline__ float row_score(const float (&p)[L::EPL], const float (&q)[L::EPL], float b, float c) {
-    float d = 0.0f;
-#pragma unroll
-    for (int e = 0; e < L::EPL; ++e) d = fmaf(p[e], q[e], d);
-    d = group_sum<L::LPU>(d);
-    return sigmoidf_ref((d + b) + c);
-}
 
 template <class L>
 __global__ void __launch_bounds__(kWave) mf_score_lists_kernel(const ScoreListArgs a) {
@@ -128,22 +108,17 @@ __global__ void __launch_bounds__(kWave) mf_score_lists_kernel(const ScoreListAr
     }
 }
 
-// the layout of `dim`: with 16-byte aligned tables the pair kernel's (dispatch_dim) at its own
-// sizes and a float4 per lane at the other multiples of 4; else the scalar-load layouts
+// the layout of `dim`: dispatch_rows' (rg_common.h), but with 16-byte aligned tables a float4 per
+// lane at the multiples of 4 that are not the pair kernel's own sizes
 template <typename F>
 int dispatch_lists(int dim, bool aligned, F &&f) {
-    if (aligned && dim % 4 == 0) {
-        if (dim == 8 || dim == 16 || dim == 32 || dim == 64 || dim == 128 || dim == 256) return dispatch_dim(dim, f);
+    const bool pair_dim = dim == 8 || dim == 16 || dim == 32 || dim == 64 || dim == 128 || dim == 256;
+    if (aligned && dim % 4 == 0 && !pair_dim) {
         if (dim <= 64) return f.template operator()<VecLayout<16>>();
         if (dim <= 128) return f.template operator()<VecLayout<32>>();
         return f.template operator()<VecLayout<64>>();
     }
-    if (dim <= 16) return f.template operator()<RowLayout<16, 1, false>>();
-    if (dim <= 32) return f.template operator()<RowLayout<16, 2, false>>();
-    if (dim <= 64) return f.template operator()<RowLayout<16, 4, false>>();
-    if (dim <= 128) return f.template operator()<RowLayout<64, 2, false>>();
-    if (dim <= 192) return f.template operator()<RowLayout<64, 3, false>>();
-    return f.template operator()<RowLayout<64, 4, false>>();
+    return dispatch_rows(dim, aligned, f);
 }
 
 struct ScoreListLaunch {
@@ -151,10 +126,8 @@ struct ScoreListLaunch {
     hipStream_t stream;
     template <class L>
     int operator()() const {
-        const int64_t blocks = (a.n + L::UPW - 1) / L::UPW;
-        if (blocks > (int64_t)INT_MAX) return fail_arg("rg_mf_score_lists: too many lists for one launch");
-        hipLaunchKernelGGL((mf_score_lists_kernel<L>), dim3((unsigned)blocks), dim3(kWave), 0, stream, a);
-        return check_launch("rg_mf_score_lists");
+        return launch_row_groups<L>(mf_score_lists_kernel<L>, a.n, a, stream, "rg_mf_score_lists",
+                                    "too many lists for one launch");
     }
 };
 

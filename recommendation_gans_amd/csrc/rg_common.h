@@ -1,6 +1,7 @@
 // Shared device helpers for librg_hip.so (gfx950 / CDNA4, wave64).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdint.h>
 #include <string>
 
@@ -448,8 +449,28 @@ struct BackLayout<RowLayout<32, 4, true>> {
     using type = RowLayoutV<16, 2>;
 };
 
-// Dispatch on dim: calls f.template operator()<Layout>() for the layout of `dim`.
-template <typename F>
+// Dispatch on dim: each of the three below calls f.template operator()<Layout>() for the layout
+// of `dim`.  MAXD (128 or 256) is the largest dim the caller takes: the layouts that only larger
+// dims reach are not instantiated for it (implicit ALS stops at 128).
+
+// The scalar-load layouts, for any dim and any alignment: dims <= 64 on 16 lanes per row (4 rows
+// per wave), the larger ones on a wave per row.
+template <int MAXD = 256, typename F>
+inline int dispatch_scalar(int dim, F &&f) {
+    if (dim < 1 || dim > MAXD) return fail_arg("dim must be in [1, " + std::to_string(MAXD) + "]");
+    if (dim <= 16) return f.template operator()<RowLayout<16, 1, false>>();
+    if (dim <= 32) return f.template operator()<RowLayout<16, 2, false>>();
+    if (dim <= 64) return f.template operator()<RowLayout<16, 4, false>>();
+    if constexpr (MAXD > 128) {
+        if (dim > 192) return f.template operator()<RowLayout<64, 4, false>>();
+        if (dim > 128) return f.template operator()<RowLayout<64, 3, false>>();
+    }
+    return f.template operator()<RowLayout<64, 2, false>>();
+}
+
+// The pair kernel's layouts, for tables whose rows take 16-byte loads: a float4 per lane at its
+// own sizes, the scalar-load layouts at every other dim.
+template <int MAXD = 256, typename F>
 inline int dispatch_dim(int dim, F &&f) {
     switch (dim) {
         case 8: return f.template operator()<RowLayout<2, 4, true>>();
@@ -457,17 +478,66 @@ inline int dispatch_dim(int dim, F &&f) {
         case 32: return f.template operator()<RowLayout<8, 4, true>>();
         case 64: return f.template operator()<RowLayout<16, 4, true>>();
         case 128: return f.template operator()<RowLayout<32, 4, true>>();
-        case 256: return f.template operator()<RowLayout<64, 4, true>>();
+        case 256:
+            if constexpr (MAXD >= 256) return f.template operator()<RowLayout<64, 4, true>>();
+            break;
         default: break;
     }
-    // other dims <= 64: 16 lanes per row (4 rows per wave) instead of a wave per row
-    if (dim >= 1 && dim <= 16) return f.template operator()<RowLayout<16, 1, false>>();
-    if (dim <= 32) return f.template operator()<RowLayout<16, 2, false>>();
-    if (dim <= 64) return f.template operator()<RowLayout<16, 4, false>>();
-    if (dim <= 128) return f.template operator()<RowLayout<64, 2, false>>();
-    if (dim <= 192) return f.template operator()<RowLayout<64, 3, false>>();
-    if (dim <= 256) return f.template operator()<RowLayout<64, 4, false>>();
-    return fail_arg("dim must be in [1, 256]");
+    return dispatch_scalar<MAXD>(dim, f);
+}
+
+// dispatch_dim when every table of the call is 16-byte aligned, else the scalar-load layouts of
+// the same lane counts: the row kernels that are handed tables they do not own.
+template <int MAXD = 256, typename F>
+inline int dispatch_rows(int dim, bool aligned, F &&f) {
+    return aligned ? dispatch_dim<MAXD>(dim, f) : dispatch_scalar<MAXD>(dim, f);
+}
+
+// ---------------------------------------------------------------- row groups
+// The parts of a kernel in which a row (a user, a list, a sequence) is owned by one group of
+// L::LPU lanes, L::UPW rows per wave: rg_mf_fold.hip, rg_cand.hip, rg_seq.hip, rg_als.hip, and the
+// MF pair, score and owner kernels.
+
+// wave-uniform maximum of a non-negative 64-bit count: the wave loops to its longest row
+__device__ __forceinline__ int64_t wave_max64(int64_t x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int64_t y = __shfl_xor(x, o);
+        x = y > x ? y : x;
+    }
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)x);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)x >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// p . q of two rows held in layout L: the lane's fmaf chain over its elements in ascending order
+// from 0, then the group's butterfly.  Every lane of the group ends with the same bits, and every
+// lane of the wave must take part.
+template <class L>
+__device__ __forceinline__ float row_dot(const float (&p)[L::EPL], const float (&q)[L::EPL]) {
+    float d = 0.0f;
+#pragma unroll
+    for (int e = 0; e < L::EPL; ++e) d = fmaf(p[e], q[e], d);
+    return group_sum<L::LPU>(d);
+}
+
+// the MF score of a (user, item) pair: sigmoid((p . q + b) + c), in that order
+template <class L>
+__device__ __forceinline__ float row_score(const float (&p)[L::EPL], const float (&q)[L::EPL], float b, float c) {
+    return sigmoidf_ref((row_dot<L>(p, q) + b) + c);
+}
+
+// Launch `kernel` (an instance for layout L) over n rows: one wave per workgroup (the waves share
+// nothing, so small workgroups spread over more compute units), ceil(n / L::UPW) workgroups.
+// `what` is the entry's name in the error texts, `too_many` the rest of the one for a grid past
+// INT_MAX.
+template <class L, class Args>
+inline int launch_row_groups(void (*kernel)(Args), int64_t n, const Args &a, hipStream_t stream, const char *what,
+                             const char *too_many) {
+    const int64_t blocks = (n + L::UPW - 1) / L::UPW;
+    if (blocks > (int64_t)INT_MAX) return fail_arg(std::string(what) + ": " + too_many);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kWave), 0, stream, a);
+    return check_launch(what);
 }
 
 }  // namespace rg

@@ -311,6 +311,8 @@ __global__ __launch_bounds__(kBlock) void mf_scores_kernel(const float *__restri
         L::load(ur, uw, u, D, sub);
         L::load(ir, iw, i, D, sub);
     }
+    // row_dot (rg_common.h) written out: through the helper the compiler allocates the two id
+    // registers the other way round, and this kernel is kept instruction for instruction
     float d = 0.0f;
 #pragma unroll
     for (int e = 0; e < EPL; ++e) d = fmaf(ur[e], ir[e], d);

@@ -8,7 +8,8 @@
 // negatives in chunks of kNC, gathering the item rows (coalesced LPU-lane row loads, served by
 // L2 after the first step), reducing the dot over the group's lanes (DPP), forming dz per pair
 // and accumulating dz * Q_i; then the update (opt_update, rg_common.h).  Nothing but the result
-// is written.
+// is written.  The layout dispatch, the score, the wave's longest row and the launch are the
+// row-group helpers of rg_common.h (dispatch_rows, row_score, wave_max64, launch_row_groups).
 //
 // Order of a user's sums: every positive first sums its own term -- its negatives' dz * Q_j with
 // j ascending, then its own dz * Q_i (and likewise its loss terms) -- and the positives' terms are
@@ -39,27 +40,6 @@ struct FoldArgs {
     int32_t steps;
     float *user_w, *user_b, *loss_out;
 };
-
-// wave-uniform maximum of a non-negative 64-bit count
-__device__ __forceinline__ int64_t wave_max64(int64_t x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const int64_t y = __shfl_xor(x, o);
-        x = y > x ? y : x;
-    }
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)x);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)x >> 32));
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
-template <class L>
-__device__ __forceinline__ float row_score(const float (&p)[L::EPL], const float (&q)[L::EPL], float b, float c) {
-    float d = 0.0f;
-#pragma unroll
-    for (int e = 0; e < L::EPL; ++e) d = fmaf(p[e], q[e], d);
-    d = group_sum<L::LPU>(d);
-    return sigmoidf_ref((d + b) + c);
-}
 
 // per-group state of one positive while its negatives are walked
 struct PosState {
@@ -245,28 +225,13 @@ __global__ void __launch_bounds__(kWave) mf_fold_kernel(const FoldArgs a) {
     }
 }
 
-// the layout of `dim`: the pair kernel's (dispatch_dim) when both tables take 16-byte loads,
-// else the scalar-load layouts of the same lane counts
-template <typename F>
-int dispatch_fold(int dim, bool aligned, F &&f) {
-    if (aligned) return dispatch_dim(dim, f);
-    if (dim <= 16) return f.template operator()<RowLayout<16, 1, false>>();
-    if (dim <= 32) return f.template operator()<RowLayout<16, 2, false>>();
-    if (dim <= 64) return f.template operator()<RowLayout<16, 4, false>>();
-    if (dim <= 128) return f.template operator()<RowLayout<64, 2, false>>();
-    if (dim <= 192) return f.template operator()<RowLayout<64, 3, false>>();
-    return f.template operator()<RowLayout<64, 4, false>>();
-}
-
 struct FoldLaunch {
     const FoldArgs &a;
     hipStream_t stream;
     template <class L>
     int operator()() const {
-        const int64_t blocks = (a.n_users + L::UPW - 1) / L::UPW;
-        if (blocks > (int64_t)INT_MAX) return fail_arg("rg_mf_fold_in_users: too many users for one launch");
-        hipLaunchKernelGGL((mf_fold_kernel<L>), dim3((unsigned)blocks), dim3(kWave), 0, stream, a);
-        return check_launch("rg_mf_fold_in_users");
+        return launch_row_groups<L>(mf_fold_kernel<L>, a.n_users, a, stream, "rg_mf_fold_in_users",
+                                    "too many users for one launch");
     }
 };
 
@@ -300,5 +265,5 @@ extern "C" int rg_mf_fold_in_users(void *stream, const float *item_w, const floa
     const FoldArgs a{item_w, item_b, dim, hist_ptr, hist_idx, neg_idx, n_neg, n_users, loss, *opt,
                      reinterpret_cast<const float2 *>(step_coef), steps, user_w, user_b, loss_out};
     const bool aligned = (((uintptr_t)item_w | (uintptr_t)user_w) & 15u) == 0;
-    return dispatch_fold(dim, aligned, FoldLaunch{a, (hipStream_t)stream});
+    return dispatch_rows(dim, aligned, FoldLaunch{a, (hipStream_t)stream});
 }

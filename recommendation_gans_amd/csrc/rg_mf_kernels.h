@@ -315,13 +315,7 @@ __device__ __forceinline__ void pairs_body(const PairsArgs &a, const int64_t blk
 #pragma unroll
         for (int e = 0; e < EPL; ++e) upos[e] = ur[0][e];
 #pragma unroll
-        for (int q = 0; q < NP; ++q) {
-            float d = 0.0f;
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) d = fmaf(ur[q][e], ir[q][e], d);
-            d = group_sum<LPU>(d);
-            p[q] = sigmoidf_ref((d + ub[q]) + ib[q]);
-        }
+        for (int q = 0; q < NP; ++q) p[q] = row_score<L>(ur[q], ir[q], ub[q], ib[q]);
     }
 
     RG_STAMP(2);

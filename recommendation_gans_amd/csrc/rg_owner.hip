@@ -80,12 +80,7 @@ __device__ __forceinline__ float score(const OwnTables &t, int lu, int i, int su
     float ur[EPL], ir[EPL];
     L::load(ur, t.user_w, lu, t.dim, sub);
     L::load(ir, t.item_w, i, t.dim, sub);
-    const float ub = t.user_b[lu], ib = t.item_b[i];
-    float d = 0.0f;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) d = fmaf(ur[e], ir[e], d);
-    d = group_sum<L::LPU>(d);
-    return sigmoidf_ref((d + ub) + ib);
+    return row_score<L>(ur, ir, t.user_b[lu], t.item_b[i]);
 }
 
 // Grid: [pos_blocks: the planned positives, units_per_block positions each]

@@ -5,7 +5,9 @@
 // rg_seq_pool_grads: a sequence is owned by one group of L::LPU lanes (the pair kernel's row
 // layout, rg_common.h: a lane holds EPL elements of every row), 64 / LPU sequences per wave, one
 // wave per workgroup (the waves share nothing).  The running sum S of the rows seen so far and
-// the non-padding count c stay in registers.
+// the non-padding count c stay in registers.  The layout dispatch, the dot and the launch are the
+// row-group helpers of rg_common.h (dispatch_rows: the vector layouts need 16-byte rows, every
+// other dim and an unaligned table take the scalar-load ones; row_dot; launch_row_groups).
 //   forward walk, t = 0 .. L-1:  r_t = S / (c + 1); the target's row and the K negatives' rows are
 //     gathered, the dots reduced over the group's lanes (DPP), the loss term and dz formed; the
 //     target-side and negative-side gradients (dz * r_t, dz) go out as float atomics; the K + 1
@@ -43,14 +45,6 @@ struct SeqArgs {
 // an id outside [0, num_items) is read as padding: no access outside the tables
 __device__ __forceinline__ int64_t safe_id(int64_t id, int64_t num_items) {
     return (uint64_t)id < (uint64_t)num_items ? id : 0;
-}
-
-template <class L>
-__device__ __forceinline__ float row_dot(const float (&p)[L::EPL], const float (&q)[L::EPL]) {
-    float d = 0.0f;
-#pragma unroll
-    for (int e = 0; e < L::EPL; ++e) d = fmaf(p[e], q[e], d);
-    return group_sum<L::LPU>(d);
 }
 
 // grad[row] += dz * (x, 1): the row's dim elements from the lanes that own them, the bias
@@ -207,10 +201,8 @@ struct SeqLaunch {
     hipStream_t stream;
     template <class L>
     int operator()() const {
-        const int64_t blocks = (a.B + L::UPW - 1) / L::UPW;
-        if (blocks > (int64_t)INT_MAX) return fail_arg("rg_seq_pool_grads: too many sequences for one launch");
-        hipLaunchKernelGGL((seq_pool_grads_kernel<L>), dim3((unsigned)blocks), dim3(kWave), 0, stream, a);
-        return check_launch("rg_seq_pool_grads");
+        return launch_row_groups<L>(seq_pool_grads_kernel<L>, a.B, a, stream, "rg_seq_pool_grads",
+                                    "too many sequences for one launch");
     }
 };
 
@@ -298,25 +290,10 @@ struct SeqReprLaunch {
     hipStream_t stream;
     template <class L>
     int operator()() const {
-        const int64_t blocks = (a.n + L::UPW - 1) / L::UPW;
-        if (blocks > (int64_t)INT_MAX) return fail_arg("rg_seq_pool_repr: too many sequences for one launch");
-        hipLaunchKernelGGL((seq_pool_repr_kernel<L>), dim3((unsigned)blocks), dim3(kWave), 0, stream, a);
-        return check_launch("rg_seq_pool_repr");
+        return launch_row_groups<L>(seq_pool_repr_kernel<L>, a.n, a, stream, "rg_seq_pool_repr",
+                                    "too many sequences for one launch");
     }
 };
-
-// the vector layouts need 16-byte rows; every other dim (and an unaligned table) takes the
-// scalar-load layouts of the same lane counts
-template <typename F>
-int dispatch_seq(int dim, bool aligned, F &&f) {
-    if (aligned) return dispatch_dim(dim, f);
-    if (dim <= 16) return f.template operator()<RowLayout<16, 1, false>>();
-    if (dim <= 32) return f.template operator()<RowLayout<16, 2, false>>();
-    if (dim <= 64) return f.template operator()<RowLayout<16, 4, false>>();
-    if (dim <= 128) return f.template operator()<RowLayout<64, 2, false>>();
-    if (dim <= 192) return f.template operator()<RowLayout<64, 3, false>>();
-    return f.template operator()<RowLayout<64, 4, false>>();
-}
 
 bool seq_dim_ok(int32_t dim) { return dim >= 4 && dim <= 256 && dim % 4 == 0; }
 
@@ -349,7 +326,7 @@ extern "C" int rg_seq_pool_grads(void *stream, const int64_t *seq, const int64_t
     float *partials = workspace + B * (int64_t)L * (K + 1);
     const SeqArgs a{seq, neg, E, b, dim, L, K, loss, B, num_items, inv_count, grad, workspace, partials};
     const bool aligned = ((uintptr_t)E & 15u) == 0;
-    const int rc = dispatch_seq(dim, aligned, SeqLaunch{a, (hipStream_t)stream});
+    const int rc = dispatch_rows(dim, aligned, SeqLaunch{a, (hipStream_t)stream});
     if (rc != RG_OK) return rc;
     hipLaunchKernelGGL(seq_loss_kernel, dim3(1), dim3(kWave), 0, (hipStream_t)stream, partials, B,
                        (double)inv_count, loss_out);
@@ -383,5 +360,5 @@ extern "C" int rg_seq_pool_repr(void *stream, const float *E, int32_t dim, int64
     if (!ids && (ptr || L > 0)) return fail_arg("rg_seq_pool_repr: ids is null");
     const SeqReprArgs a{E, ids, ptr, dim, L, n, num_items, out};
     const bool aligned = (((uintptr_t)E | (uintptr_t)out) & 15u) == 0;
-    return dispatch_seq(dim, aligned, SeqReprLaunch{a, (hipStream_t)stream});
+    return dispatch_rows(dim, aligned, SeqReprLaunch{a, (hipStream_t)stream});
 }

@@ -4,7 +4,7 @@ one dtype, the list summed forward, reversed or pairwise -- and ``E32``: the lar
 three float32 restatements from the float64 one over a case's elements, which is the error a float32
 evaluation of the same formulas has.
 
-The cases cover every row layout the kernels are instantiated for (rg_als.hip dispatch_als; LPU
+The cases cover every row layout the kernels are instantiated for (rg_common.h dispatch_rows<128>; LPU
 lanes x EPL elements per lane), by dim:
     8 / 16 / 32 / 64 / 128   the 16-byte layouts of 2 / 4 / 8 / 16 / 32 lanes x 4
     1, 3                     scalar, 16 lanes x 1        24    scalar, 16 lanes x 2
@@ -206,7 +206,8 @@ WAVES, WAVE, LDS_CU = 8, 64, 160 * 1024
 
 
 def aligned_layout(dim):
-    """(LPU, EPL) of an aligned call at ``dim`` (rg_als.hip dispatch_als)."""
+    """(LPU, EPL) of an aligned call at ``dim`` (rg_common.h dispatch_rows, which rg_als.hip caps at
+    dim 128)."""
     if dim in (8, 16, 32, 64, 128):
         return dim // 4, 4
     return (16, 1) if dim <= 16 else (16, 2) if dim <= 32 else (16, 4) if dim <= 64 else (64, 2)

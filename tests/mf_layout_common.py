@@ -3,7 +3,9 @@ here, and nothing from the GPU side is imported).
 
 Every kernel that walks embedding rows takes its lane layout from ``dim`` through ``dispatch_dim``
 (csrc/rg_common.h): ``RowLayout<LPU, EPL, VEC>`` spreads a row over LPU lanes with EPL elements
-per lane.
+per lane.  The scalar layouts are one ladder, ``dispatch_scalar``, which is ``dispatch_dim``'s tail;
+the kernels that are handed tables they do not own (fold-in, list scoring, ALS, the sequence model)
+go through ``dispatch_rows``: ``dispatch_dim`` on 16-byte aligned tables, ``dispatch_scalar`` else.
 
 * float4 (``VEC``), one float4 per lane, no mask:
   8 -> ``<2,4,true>``, 16 -> ``<4,4,true>``, 32 -> ``<8,4,true>``, 64 -> ``<16,4,true>``,
@@ -22,8 +24,9 @@ the one layout whose elements per lane are no power of two, also its full row 19
 mask and, not being one of dispatch_dim's six sizes, takes scalar loads although 192 % 4 == 0.
 ``<16,1>`` starts at 1 (a row on lane 0 alone).
 
-rg_mf_score_lists has a dispatch of its own (csrc/rg_cand.hip); tests/candidates_common.py lists its
-dims by layout."""
+rg_mf_score_lists adds one branch of its own to ``dispatch_rows`` (csrc/rg_cand.hip: ``VecLayout``,
+a float4 per lane at the aligned multiples of 4 off the six sizes); tests/candidates_common.py lists
+its dims by layout."""
 
 LAYOUT_DIMS = {
     "<16,1>": [1, 7, 15],

@@ -95,7 +95,7 @@ def run_views(case, cg, off_other, off_x):
 @pytest.mark.parametrize("which", ["other_table and x_inout", "x_inout alone"])
 @pytest.mark.parametrize("i", ac.UNALIGNED, ids=[ac.CASE_IDS[i] for i in ac.UNALIGNED])
 def test_tables_off_a_16_byte_boundary_meet_the_float64_restatement(i, which):
-    """The unaligned dispatch (dispatch_als's scalar layouts), held to float64 by the parity test's
+    """The unaligned dispatch (dispatch_rows' scalar layouts), held to float64 by the parity test's
     own rule; at dim 24 the aligned call selects the same layout, so the bits are the aligned call's."""
     d = ac.case_data(i)
     assert d["admitted"], (d["e32"], d["xmax"])

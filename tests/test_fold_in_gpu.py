@@ -111,7 +111,7 @@ def run_entry(case, loss, steps, wd, off_items, off_users):
 @pytest.mark.parametrize("which", ["item_w and user_w", "user_w alone"])
 @pytest.mark.parametrize("i", fc.UNALIGNED, ids=[fc.CASE_IDS[i] for i in fc.UNALIGNED])
 def test_tables_off_a_16_byte_boundary_meet_the_float64_reference(i, which):
-    """The unaligned dispatch (dispatch_fold's scalar layouts), held to float64 by the parity test's
+    """The unaligned dispatch (dispatch_rows' scalar layouts), held to float64 by the parity test's
     own rule; at dim 24 the aligned call selects the same layout, so the bits are the aligned call's."""
     d = fc.case_data(i)
     case = d["case"]

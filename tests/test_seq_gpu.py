@@ -79,7 +79,7 @@ def _guards_hold(buf, off, size):
 
 @pytest.mark.parametrize("i", sc.UNALIGNED, ids=[sc.CASE_IDS[i] for i in sc.UNALIGNED])
 def test_pool_grads_on_a_table_off_a_16_byte_boundary(i):
-    """The unaligned dispatch (dispatch_seq's scalar layouts) under the oracle test's own rule; at
+    """The unaligned dispatch (dispatch_rows' scalar layouts) under the oracle test's own rule; at
     d 24 the aligned call selects the same layout, so the loss (fixed-order sums) has its bits."""
     data = sc.case_data(i)
     case, loss, d = data["case"], data["loss"], data["case"]["d"]
@@ -234,7 +234,7 @@ def repr_entry(E, ids, ptr, L, n, out, num_items):
 @pytest.mark.parametrize("which", ["E and out", "out alone"])
 @pytest.mark.parametrize("d", [8, 16, 64, 128, 24])
 def test_pool_repr_on_tables_off_a_16_byte_boundary(d, which):
-    """The unaligned dispatch (dispatch_seq's scalar layouts) inside the oracle test's own bound,
+    """The unaligned dispatch (dispatch_rows' scalar layouts) inside the oracle test's own bound,
     padded and ragged; at d 24 the aligned call selects the same layout and gives the same bits."""
     n, L, N = 67, 33, 257
     rs = np.random.RandomState(n + L + d)
