@@ -19,14 +19,17 @@ LIB = os.path.join(PKG, "librg_hip.so")
 ARCH = os.environ.get("RG_OFFLOAD_ARCH", "gfx950")
 
 SOURCES = ["rg_api.cpp", "rg_sampler.hip", "rg_mf.hip", "rg_mf_alt.hip", "rg_stepper.cpp", "rg_stepper_alt.cpp",
-           "rg_comm.cpp", "rg_mtjump.cpp", "rg_ncf.hip", "rg_gemm.hip", "rg_gan.hip", "rg_eval.hip", "rg_plan.hip",
+           "rg_comm.cpp", "rg_mtjump.cpp", "rg_ncf.hip", "rg_ncf_tile.hip", "rg_ncf_wave.hip", "rg_gemm.hip",
+           "rg_gan.hip", "rg_eval.hip", "rg_plan.hip",
            "rg_owner.hip", "rg_uniform.hip", "rg_membw.hip", "rg_pool.cpp", "rg_ncf_score.hip",
            "rg_mf_score.hip", "rg_mf_topk.hip", "rg_item_sim.hip", "rg_topk_wide.hip", "rg_gan_score.hip",
            "rg_mf_fold.hip", "rg_cand.hip", "rg_diverse.hip", "rg_als.hip", "rg_seq.hip"]
 HEADERS = ["rg_common.h", "rg_gemm.h", "rg_mt.h", "rg_owner.h", "rg_mlp_update.h", "rg_mfma.h", "rg_mf_kernels.h",
-           "rg_stepper.h", "rg_mf_score_tile.h", "rg_topk_lists.h", "rg_topk_tiles.h"]
-# the two MF translation units share rg_mf_kernels.h, which -D defines reach: always built together
+           "rg_stepper.h", "rg_mf_score_tile.h", "rg_topk_lists.h", "rg_topk_tiles.h", "rg_ncf.h"]
+# the two MF translation units share rg_mf_kernels.h, which -D defines reach: always built together;
+# likewise the NCF step's three (the host API and its two pair kernels, sharing rg_ncf.h)
 MF_UNIT = ("rg_mf.hip", "rg_mf_alt.hip")
+NCF_UNIT = ("rg_ncf.hip", "rg_ncf_tile.hip", "rg_ncf_wave.hip")
 
 
 def _hipcc():
@@ -58,7 +61,8 @@ def build(force=False, verbose=False, jobs=8, diag=False, variant=None, defines=
     the product never loads it).  variant=NAME: _variants/librg_hip_NAME.so built with the
     extra -D defines, for same-box A/B runs (scripts load it through RG_LIB).  only=[src, ...]
     (variants): compile just those sources with the defines and link the product's objects
-    for the rest; rg_mf.hip and rg_mf_alt.hip are one unit (naming either compiles both)."""
+    for the rest; rg_mf.hip and rg_mf_alt.hip are one unit (naming either compiles both), and so
+    are rg_ncf.hip, rg_ncf_tile.hip and rg_ncf_wave.hip."""
     if variant:
         os.makedirs(os.path.join(PKG, "_variants"), exist_ok=True)
         lib = os.path.join(PKG, "_variants", f"librg_hip_{variant}.so")
@@ -72,8 +76,9 @@ def build(force=False, verbose=False, jobs=8, diag=False, variant=None, defines=
     common = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-I", os.path.join(ROOT, "include"),
               "-Wall", "-Wno-unused-function", "-ffp-contract=fast"] + (["-DRG_DIAG_STAMPS"] if diag else []) + \
         (os.environ.get("RG_EXTRA_CFLAGS", "").split() if diag else []) + [f"-D{d}" for d in defines]
-    if only and any(s in MF_UNIT for s in only):
-        only = list(only) + list(MF_UNIT)
+    for unit in (MF_UNIT, NCF_UNIT):
+        if only and any(s in unit for s in only):
+            only = list(only) + list(unit)
     procs, objs = [], []
     for s in SOURCES:
         src = os.path.join(CSRC, s)

@@ -1,5 +1,5 @@
-// What the MFMA kernels of rg_ncf.hip and rg_ncf_score.hip share: the 4-float vector of an MFMA
-// operand / accumulator, the fp32 16x16x4 instruction and a compile-time loop.
+// What the MFMA kernels of rg_ncf_tile.hip, rg_ncf_wave.hip and rg_ncf_score.hip share: the
+// 4-float vector of an MFMA operand / accumulator, the fp32 16x16x4 instruction and a compile-time loop.
 #pragma once
 #include <utility>
 

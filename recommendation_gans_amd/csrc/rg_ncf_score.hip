@@ -12,7 +12,7 @@
 //   scores   grid (item tile of 64, group of 64 users), 4 waves; wave w owns the group's users
 //            [16 w, 16 w + 16).  A lane (g = lane / 16, j = lane % 16) keeps its slice of the
 //            tile's Hi rows in registers for every user (item 16 nb + j of block nb, features
-//            16 t + 4 g .. + 3: the MFMA's B / C layout, as ncfw::fwd of rg_ncf.hip), so per
+//            16 t + 4 g .. + 3: the MFMA's B / C layout, as ncfw::fwd1 of rg_ncf_wave.hip), so per
 //            (user, 16 items) the first layer is an add and a LeakyReLU.  The narrow layers
 //            E -> E/2 -> .. -> 8 run on __builtin_amdgcn_mfma_f32_16x16x4f32 with the weights in
 //            LDS (row-major [out][in + 4], the 8-wide layer padded to 16 rows of zeros), each
@@ -32,7 +32,7 @@
 // kernel of their own below (rg_ncf_score_pairs), which shares the tower and the LDS weight layout.
 #include <climits>
 
-#include "rg_common.h"
+#include "rg_ncf.h"
 #include "rg_mfma.h"
 
 namespace rg {
@@ -50,14 +50,8 @@ __host__ __device__ constexpr int im_stride(int mp) { return mp + 2; }
 
 // layer k maps H(k) = 2E >> k features to H(k + 1); k = 0 is the split layer, k = NH the output
 template <int E>
-struct Shape {
-    static constexpr int NH = E == 8 ? 1 : E == 16 ? 2 : E == 32 ? 3 : 4;
-    static constexpr int H(int k) { return (2 * E) >> k; }
-    static constexpr int w_off(int k) {       // flat parameter offset of layer k (W then b)
-        int o = 0;
-        for (int j = 0; j < k; ++j) o += H(j + 1) * H(j) + H(j + 1);
-        return o;
-    }
+struct Shape : NcfTower<E> {
+    using NcfTower<E>::H;
     // a layer in LDS: row-major [rows(k)][S(k)], the rows padded to 16 with zeros
     static constexpr int tiles(int k) { return H(k) < 16 ? 1 : H(k) / 16; }   // 16-feature tiles of layer k's input
     static constexpr int rows(int k) { return 16 * tiles(k + 1); }
@@ -442,17 +436,6 @@ int score_check_model(const rg_ncf_model_t *m, int64_t n, const char *count, boo
     return RG_OK;
 }
 
-// Dispatch on the embedding width: calls f.template operator()<E>() (dim as score_check_shape left it).
-template <typename F>
-int dispatch_width(int dim, F &&f) {
-    switch (dim) {
-        case 8: return f.template operator()<8>();
-        case 16: return f.template operator()<16>();
-        case 32: return f.template operator()<32>();
-        default: return f.template operator()<64>();
-    }
-}
-
 struct ScoreLaunch {
     hipStream_t s;
     const rg_ncf_model_t *m;
@@ -460,8 +443,9 @@ struct ScoreLaunch {
     int64_t n_users;
     float *ws, *out;
     int64_t ld;
-    template <int E>
-    int operator()() const {
+    template <class EC>
+    int operator()(EC) const {
+        constexpr int E = EC::value;
         const int MP = pad4(m->mf_dim);
         float *Hi = ws, *Hu = Hi + m->num_items * E, *Gu = Hu + n_users * E;
         const HalvesArgs h{m->user_w, m->item_w, m->mlp, m->mf_user_w, users, m->num_items, n_users, m->mf_dim, MP, Hi, Hu, Gu};
@@ -496,8 +480,9 @@ struct PairsLaunch {
     const int64_t *users, *items;
     int64_t n;
     float *out;
-    template <int E>
-    int operator()() const {
+    template <class EC>
+    int operator()(EC) const {
+        constexpr int E = EC::value;
         const int MP = pad4(m->mf_dim);
         const int64_t tiles = (n + kPairTile - 1) / kPairTile, cap = pairs_resident<E>(MP);
         const PairArgs a{m->user_w, m->item_w, m->mlp, m->mf_user_w, m->mf_item_w, users, items, n, tiles, m->mf_dim, MP, out};
@@ -519,7 +504,7 @@ extern "C" int rg_ncf_score_pairs(void *stream, const rg_ncf_model_t *m, const i
     if ((uintptr_t)m->user_w % 16 || (uintptr_t)m->item_w % 16)
         return fail_arg("rg_ncf_score_pairs: the embedding tables must be 16-byte aligned");
     if (n == 0) return RG_OK;
-    return dispatch_width(m->dim, PairsLaunch{(hipStream_t)stream, m, users_dev, items_dev, n, out_dev});
+    return dispatch_ncf_dim(m->dim, PairsLaunch{(hipStream_t)stream, m, users_dev, items_dev, n, out_dev});
 }
 
 extern "C" int64_t rg_ncf_score_workspace_len(const rg_ncf_model_t *m, int64_t n_users) {
@@ -536,5 +521,5 @@ extern "C" int rg_ncf_score_users(void *stream, const rg_ncf_model_t *m, const i
     if (n_users == 0) return RG_OK;
     if ((n_users + kGroup - 1) / kGroup > 65535 || (m->num_items + kHalfRows - 1) / kHalfRows > INT_MAX / 2)
         return fail_arg("rg_ncf_score_users: too many users or items for one launch");
-    return dispatch_width(m->dim, ScoreLaunch{(hipStream_t)stream, m, users_dev, n_users, workspace_dev, out_dev, ld});
+    return dispatch_ncf_dim(m->dim, ScoreLaunch{(hipStream_t)stream, m, users_dev, n_users, workspace_dev, out_dev, ld});
 }

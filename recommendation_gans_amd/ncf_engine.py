@@ -412,7 +412,7 @@ class NCFEngine:
 
         The ``nr`` slots after the rows of ``[nr*D | nr | 0]`` are the MF path's bias gradients.
         The NCF tables have no bias (has_bias = false), and the pair kernel stores every list
-        entry with the weight 1.0 beside its contribution row (rg_ncf.hip store_entry), so the
+        entry with the weight 1.0 beside its contribution row (the pair kernels' store_entry), so the
         slot is the sum of those weights: the number of the row's list entries this step,
         min(examples that claimed a slot of the row, RG_MF_LIST_CAP) -- every valid example for a
         user, every valid example but the planned positives for an item -- and 0 for an untouched

@@ -1,5 +1,6 @@
 # GPU box: same-box A/B of NCF library variants (python -m recommendation_gans_amd.build --variant NAME
-# --only rg_ncf.hip ...).  The NCF / NeuMF GPU tests against every non-base variant first, then per
+# --only rg_ncf.hip,rg_ncf_tile.hip,rg_ncf_wave.hip -D...: the step's three units are built together, naming
+# any one compiles all three).  The NCF / NeuMF GPU tests against every non-base variant first, then per
 # variant, interleaved twice: the NCF bench line and a rocprofv3 kernel-trace of it (average
 # ncf_wave_kernel and tail-launch durations).
 # Usage: [NCFMODEL=neumf] bash scripts/gpu_ncf_lib_ab.sh TAG base NAME ...

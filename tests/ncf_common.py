@@ -7,7 +7,7 @@ tests/ncf_grad_common.py, which builds on the pieces below.
 * ``make_params``: an NCF tower (M = 0) or a NeuMF model in named_parameters() order, initialised
   as the reference initialises them (N(0, 1) embeddings, Xavier-uniform weights, bias 0.01).
 * ``device_masks``: the device dropout RNG restated in NumPy from the kernel's definition
-  (rg_ncf.hip hash32 / mix32, the row key, the keep bit; documented on rg_ncf_work_t.seed in
+  (rg_ncf.h hash32 / mix32, the row key, the keep bit; documented on rg_ncf_work_t.seed in
   include/rg_hip.h), with uint64 / uint32 wrap-around.
 * ``parity_ratio``: how much of oracle.mf.tensor_parity's allowance a tensor uses (reporting
   only; the verdict is always tensor_parity's own).
@@ -26,7 +26,7 @@ MASK64 = (1 << 64) - 1
 
 
 def hash32(x):
-    """rg_ncf.hip hash32: murmur3's 64-bit finaliser, low 32 bits.  x: uint64 array."""
+    """rg_ncf.h hash32: murmur3's 64-bit finaliser, low 32 bits.  x: uint64 array."""
     x = np.asarray(x, dtype=np.uint64).copy()
     with np.errstate(over="ignore"):
         x ^= x >> np.uint64(33)
@@ -38,7 +38,7 @@ def hash32(x):
 
 
 def mix32(h):
-    """rg_ncf.hip mix32: murmur3 fmix32.  h: uint32 array."""
+    """rg_ncf.h mix32: murmur3 fmix32.  h: uint32 array."""
     h = np.asarray(h, dtype=np.uint32).copy()
     with np.errstate(over="ignore"):
         h ^= h >> np.uint32(16)

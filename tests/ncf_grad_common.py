@@ -28,7 +28,7 @@ with g64 the float64 oracle's gradient of the same step from the same fp32 opera
       rounding of the kink moves the element;
 * q   the overflow accumulators' fixed-point quantum times the number of terms of the element.
       rg_common.h: to_fix(v) = round(v * 2^48) (kFixScale = 2^48, __double2ll_rn), and a row that
-      overflowed its list sums ALL of its contributions that way -- the surplus where rg_ncf.hip
+      overflowed its list sums ALL of its contributions that way -- the surplus where the pair kernel
       writes hot_grad / mf_hot_grad (fix_add), the listed ones in the pull (rg_mf_kernels.h
       gf += to_fix(dz * o)).  Each term is off by at most half a quantum, 2^-49; q = 2^-48 *
       (examples of the step that touch the row) bounds the sum with a factor two to spare (the

@@ -1,5 +1,5 @@
 """What the device dropout RNG draws (production training: masks=None).  The hash per (step,
-example, unit) is restated in NumPy (tests/ncf_common.py device_masks, from rg_ncf.hip hash32 /
+example, unit) is restated in NumPy (tests/ncf_common.py device_masks, from rg_ncf.h hash32 /
 mix32, the row key and the keep bit; the contract on rg_ncf_work_t.seed in include/rg_hip.h).
 
 Per configuration -- the wave kernel (E = 64), the tile kernel (E = 16, 32), NeuMF (E = 8,

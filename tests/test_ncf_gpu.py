@@ -1,4 +1,5 @@
-"""NCF MLP step on the GPU (rg_ncf.hip through the C-ABI) against the reference's
+"""NCF MLP step on the GPU (rg_ncf.hip and its pair kernels, rg_ncf_tile.hip and
+rg_ncf_wave.hip, through the C-ABI) against the reference's
 own NCF steps (tests/golden/mlp_*.npz, dropout masks recorded from the reference
 and fed to the kernel): loss, MT stream, and every parameter after each Adam
 step (tensor parity vs the fp32 reference; small tensors vs the fp64 restatement

@@ -1,5 +1,6 @@
-"""The NCF / NeuMF training kernels (rg_ncf.hip: the wave kernel at E = 64, the tile kernel at
-E in {8, 16, 32}, with and without the GMF branch) beyond the Adam path the sibling files hold:
+"""The NCF / NeuMF training kernels (rg_ncf_wave.hip: the wave kernel at E = 64; rg_ncf_tile.hip:
+the tile kernel at E in {8, 16, 32} and at NeuMF's E = 64, with and without the GMF branch) beyond
+the Adam path the sibling files hold:
 the SGD and RMSprop tails (rg_mlp_update.h, rg_common.h) against oracle.mf.Optim, every loss at
 the tile kernel's other widths, batch sizes around the tile's column count, a partial last batch
 with the full n * batch_size draw (implicit.py:347-364), and the eval-mode loss of
@@ -78,6 +79,19 @@ TILE_CASES = [(8, "pointwise", 1, False), (8, "bpr", 3, True), (8, "hinge", 8, F
 @pytest.mark.parametrize("E,loss,n,planned", TILE_CASES)
 def test_ncf_tile_kernel_widths_and_losses(E, loss, n, planned):
     nc.run_parity(E, 0, loss, "adam", n, B=500, U=300, I=200, planned=planned, seed=E + n)
+
+
+# ---------------------------------------------------------------------------- NeuMF at E = 64
+# ncf_pairs_kernel<64, *>: the 512-thread tile kernel, where a tile's ids and list slots run one
+# tile ahead (kPipe).  Its LDS admits one workgroup per CU, so 256 workgroups: the batches are
+# the smallest at which some workgroup takes a second tile (267 and 280 tiles).
+@pytest.mark.parametrize("loss,n,B,planned", [("pointwise", 8, 800, True), ("bpr", 5, 1400, False)])
+def test_neumf_e64_tile_kernel_second_round(loss, n, B, planned):
+    from recommendation_gans_amd import _lib
+    lib = _lib.load()
+    assert lib.rg_ncf_rows_per_tile(64, 8) == 32
+    assert lib.rg_ncf_blocks(B, n, 64, 8) < lib.rg_ncf_tiles(B, n, 64, 8)
+    nc.run_parity(64, 8, loss, "adam", n, B=B, U=300, I=200, planned=planned, seed=64 + 8 + n)
 
 
 # ---------------------------------------------------------------------------- batch edges

@@ -1,7 +1,7 @@
-"""The E = 64 NCF kernel (one wave per 32-row tile, rg_ncf.hip ncf_wave_kernel) on every loss
+"""The E = 64 NCF kernel (one wave per 48-row tile, rg_ncf_wave.hip ncf_wave_kernel) on every loss
 and on tile shapes other than the bench's: BPR / hinge (pairwise, the positive's lane sums its
 column), adaptive hinge (the scores phase, then the given-dp phase), pointwise, with 1 to 8
-negatives (16, 8, 5, 4 or 3 columns per 32-row tile), with and without item plans, tables small
+negatives (24, 12, 8, 6 or 5 columns per 48-row tile), with and without item plans, tables small
 enough that hot rows overflow their per-row lists.  Two native steps with recorded dropout
 masks against the oracle (oracle/ncf.py, spotlight/losses.py:20-172 + mlp.py:5-46 restated)
 run in fp32 and fp64 from the same MLP(...) init: MT state bit-exact, loss 1e-5 relative,

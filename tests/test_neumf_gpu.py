@@ -1,4 +1,4 @@
-"""NeuMF step on the GPU (rg_ncf.hip with the GMF branch + rg_neumf_apply through the
+"""NeuMF step on the GPU (rg_ncf_tile.hip with the GMF branch + rg_neumf_apply through the
 C-ABI) against the reference's own NeuMF steps (tests/golden/neumf_*.npz, recorded
 dropout masks fed to the kernel): loss, MT stream and every parameter after each Adam
 step (tensor parity vs the fp32 reference; vs the fp64 restatement as in
