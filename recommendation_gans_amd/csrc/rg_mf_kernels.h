@@ -205,6 +205,18 @@ constexpr int kLdsFloats = 5 * kPairBlock;   // >= units per block * (dim + 1) f
 // dot product except the positive's user row, which feeds the planned item-side
 // partial sums; the rare list-overflow path re-gathers.
 //
+// One lane per pair: the dot products are reduced across the unit, so all LPU lanes hold
+// all of them; what follows a dot product is per pair, not per element, and lane
+// q % LPU alone does it for pair q (in rounds of LPU pairs where 1 + n > LPU) -- its two
+// bias gathers, sigmoid((dot + b) + c), the transcendental part of its loss term (the BPR
+// sigmoid, the hinge margin, the pointwise log and division) and its dz.  The positive's
+// score and each negative's term are broadcast back by shuffles with constant lanes, and
+// every lane forms the unit's sums (la, lb, the positive's dL/dp) from them, k = 1..n
+// left to right: each value comes from the instruction sequence it always came from, on
+// the same operands (same bits); a wave runs ceil((1 + n) / LPU) sigmoid chains per phase
+// instead of 1 + n.  Nothing indexes a register array by a lane-dependent pair: own ids
+// come from the record, own dots by a select over constant indices, dz goes through LDS.
+//
 // List tasks: t = 2q + side (side 0: user row of pair q, 1: its item row), spread
 // over the unit's lanes as t = sub + j*LPU.  With a plan, the positives are
 // processed in item-sorted order and the positive's item side (t = 1, the Zipf-hot
@@ -215,6 +227,7 @@ __device__ __forceinline__ void pairs_body(const PairsArgs &a, const int64_t blk
     constexpr int LPU = L::LPU, EPL = L::EPL, NP = NMAX + 1;
     constexpr int UPB = kPairBlock / LPU;                  // units per block
     constexpr int TPL = (2 * NP + LPU - 1) / LPU;      // list tasks per lane
+    constexpr int R = (NP + LPU - 1) / LPU;            // rounds of own pairs per lane
     constexpr bool kBackward = (PHASE == kFused) || (PHASE == kAdaptBwd);
     constexpr bool kScoresFromBuf = (PHASE == kAdaptBwd) || (PHASE == kAdaptLoss);
     __shared__ float red[2][kPairBlock / kWave];
@@ -272,6 +285,18 @@ __device__ __forceinline__ void pairs_body(const PairsArgs &a, const int64_t blk
         ti[j] = e.y & idm;
         slot[j] = claimed ? (int)(((uint32_t)((t & 1) ? e.y : e.x) >> kSlotShift) & 15u) : 0;
     }
+    // each lane's own pairs (q = sub + r*LPU), from the record for the same reason: their
+    // biases are one gather per table and round, issued with the row gathers
+    int mu[R], mi[R];
+    bool vm[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int q = sub + r * LPU;
+        vm[r] = q < NP && q <= n && (q == 0 ? has_pos : (!kScoresFromBuf && negs && active && (has_pos || !pairwise)));
+        const int2 e = rec[vm[r] ? q : 0];
+        mu[r] = e.x & idm;
+        mi[r] = e.y & idm;
+    }
     RG_STAMP(1);
     if (RG_DIAG_FLAG(3)) return;
 
@@ -288,50 +313,73 @@ __device__ __forceinline__ void pairs_body(const PairsArgs &a, const int64_t blk
     }
 
     // ---- gather rows, scores ---------------------------------------------------
-    float p[NP];
+    // pm[r]: the score of this lane's own pair q = sub + r*LPU; p0: the positive's, on every lane
+    float pm[R], p0;
     float upos[EPL];      // the positive's user row (planned item-side partial sums)
     L::zero(upos);
     if (kScoresFromBuf) {
-        p[0] = has_pos ? a.scores[s] : 0.5f;
+        p0 = has_pos ? a.scores[s] : 0.5f;
 #pragma unroll
-        for (int q = 1; q < NP; ++q) p[q] = 0.5f;
+        for (int r = 0; r < R; ++r) pm[r] = p0;   // only pair 0 (lane sub 0) is used
         if (plan && kBackward) L::load(upos, a.user_w, uid[0], D, sub);
     } else {
-        float ur[NP][EPL], ir[NP][EPL], ub[NP], ib[NP];
+        float ur[NP][EPL], ir[NP][EPL], ub[R], ib[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            if constexpr (SC1) {   // rows written by this launch's hot workgroups (mf_pipe_kernel)
+                ub[r] = L::load1_sc1(a.user_b + mu[r]);
+                ib[r] = L::load1_sc1(a.item_b + mi[r]);
+            } else {
+                ub[r] = a.user_b[mu[r]];
+                ib[r] = a.item_b[mi[r]];
+            }
+        }
 #pragma unroll
         for (int q = 0; q < NP; ++q) {
-            if constexpr (SC1) {   // rows written by this launch's hot workgroups (mf_pipe_kernel)
+            if constexpr (SC1) {
                 L::load_sc1(ur[q], a.user_w, uid[q], D, sub);
                 L::load_sc1(ir[q], a.item_w, iid[q], D, sub);
-                ub[q] = L::load1_sc1(a.user_b + uid[q]);
-                ib[q] = L::load1_sc1(a.item_b + iid[q]);
             } else {
                 L::load(ur[q], a.user_w, uid[q], D, sub);
                 L::load(ir[q], a.item_w, iid[q], D, sub);
-                ub[q] = a.user_b[uid[q]];
-                ib[q] = a.item_b[iid[q]];
             }
         }
 #pragma unroll
         for (int e = 0; e < EPL; ++e) upos[e] = ur[0][e];
+        float dot[NP];
 #pragma unroll
-        for (int q = 0; q < NP; ++q) p[q] = row_score<L>(ur[q], ir[q], ub[q], ib[q]);
+        for (int q = 0; q < NP; ++q) dot[q] = row_dot<L>(ur[q], ir[q]);
+        // the unit's lanes all hold every dot product: lane q % LPU alone adds pair q's biases
+        // and takes its sigmoid (row_score's order: sigmoid((dot + b) + c))
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            float d = dot[r * LPU];
+#pragma unroll
+            for (int c = 1; c < LPU && r * LPU + c < NP; ++c) d = (sub == c) ? dot[r * LPU + c] : d;
+            pm[r] = sigmoidf_ref((d + ub[r]) + ib[r]);
+        }
+        p0 = __shfl(pm[0], ubase);
     }
 
     RG_STAMP(2);
     // ---- loss terms and dL/dp ---------------------------------------------------
+    // Each lane does the transcendental part of its own pairs' terms; the unit's sums (la, lb,
+    // dL/dp of the positive) are then taken on every lane from the broadcast terms, k = 1..n in
+    // order.  Shuffles sit outside the lane-dependent conditions: every lane takes part.
     float la = 0.0f, lb = 0.0f;
-    float dp[NP];
+    float dp0 = 0.0f;      // dL/dp of the positive (every lane)
+    float dpm[R];          // dL/dp of the lane's own pairs
 #pragma unroll
-    for (int q = 0; q < NP; ++q) dp[q] = 0.0f;
+    for (int r = 0; r < R; ++r) dpm[r] = 0.0f;
     if (PHASE == kAdaptFwd) {
-        if (sub == 0 && has_pos) a.scores[s] = p[0];
+        if (sub == 0 && has_pos) a.scores[s] = p0;
         const int64_t col = a.perm ? (int64_t)a.perm[active ? s : 0] : s;
 #pragma unroll
-        for (int k = 0; k < NMAX; ++k) {
-            if (valid[k + 1] && sub == 0) {
-                const int64_t j = (int64_t)k * a.global_cols + a.col_offset + col;
-                const unsigned long long key = ((unsigned long long)__float_as_uint(p[k + 1]) << 32) |
+        for (int r = 0; r < R; ++r) {
+            const int q = sub + r * LPU;
+            if (vm[r] && q >= 1) {
+                const int64_t j = (int64_t)(q - 1) * a.global_cols + a.col_offset + col;
+                const unsigned long long key = ((unsigned long long)__float_as_uint(pm[r]) << 32) |
                                                (unsigned long long)(0xFFFFFFFFu - (uint32_t)j);
                 atomicMax(a.max_key, key);
             }
@@ -340,61 +388,75 @@ __device__ __forceinline__ void pairs_body(const PairsArgs &a, const int64_t blk
         if (has_pos) {
             const unsigned long long key = *a.max_key;
             const float m = __uint_as_float((uint32_t)(key >> 32));
-            const float x = (m - p[0]) + 1.0f;
+            const float x = (m - p0) + 1.0f;
             la = fmaxf(x, 0.0f);
             if (x >= 0.0f) {
-                dp[0] = -(1.0f / a.n_a);
+                dp0 = -(1.0f / a.n_a);
                 if (PHASE == kAdaptBwd && sub == 0) atomicAdd(a.active_count, 1);
             }
         }
+        if (sub == 0) dpm[0] = dp0;
     } else if (a.loss == RG_LOSS_POINTWISE || a.loss == RG_LOSS_POINTWISE_POS) {
-        if (has_pos) {
-            la = -fmaxf(logf(p[0]), -100.0f);
-            dp[0] = ((p[0] - 1.0f) / fmaxf((1.0f - p[0]) * p[0], 1e-12f)) / a.n_a;
+        // the positive: -max(log p, -100) and ((p - 1) / max((1 - p) p, 1e-12)) / n_a;
+        // a negative:   -max(log(1 - p), -100) and (p / max((1 - p) p, 1e-12)) / n_b
+        float tm[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const bool pos = sub + r * LPU == 0;
+            const float pq = pm[r];
+            tm[r] = -fmaxf(logf(pos ? pq : 1.0f - pq), -100.0f);
+            const float d = ((pos ? pq - 1.0f : pq) / fmaxf((1.0f - pq) * pq, 1e-12f)) / (pos ? a.n_a : a.n_b);
+            if (vm[r]) dpm[r] = d;
         }
+        if (has_pos) la = tm[0];   // lane sub 0's is the positive's; the loss sum reads that lane only
 #pragma unroll
         for (int k = 1; k < NP; ++k) {
-            if (valid[k]) {
-                lb += -fmaxf(logf(1.0f - p[k]), -100.0f);
-                dp[k] = (p[k] / fmaxf((1.0f - p[k]) * p[k], 1e-12f)) / a.n_b;
-            }
+            const float t = __shfl(tm[k / LPU], ubase + k % LPU);
+            if (valid[k]) lb += t;
         }
     } else {  // bpr / hinge on the neg.view(n, B) pairing
         const float g = 1.0f / a.n_a;
-        if (has_pos) {
+        const bool bpr = a.loss == RG_LOSS_BPR;
+        float om[R];   // own negative: sigmoid(p0 - p) (bpr), (p - p0) + 1 (hinge)
 #pragma unroll
-            for (int k = 1; k < NP; ++k) {
-                if (valid[k]) {
-                    if (a.loss == RG_LOSS_BPR) {
-                        const float sg = sigmoidf_ref(p[0] - p[k]);
-                        la += 1.0f - sg;
-                        const float dx = (-g) * (1.0f - sg) * sg;
-                        dp[0] += dx;
-                        dp[k] = -dx;
-                    } else {
-                        const float x = (p[k] - p[0]) + 1.0f;
-                        la += fmaxf(x, 0.0f);
-                        const float dx = x >= 0.0f ? g : 0.0f;
-                        dp[0] -= dx;
-                        dp[k] = dx;
-                    }
+        for (int r = 0; r < R; ++r) {
+            if (bpr) om[r] = sigmoidf_ref(p0 - pm[r]);
+            else om[r] = (pm[r] - p0) + 1.0f;
+        }
+#pragma unroll
+        for (int k = 1; k < NP; ++k) {
+            const float o = __shfl(om[k / LPU], ubase + k % LPU);
+            if (has_pos && valid[k]) {
+                float dk;
+                if (bpr) {
+                    const float sg = o;
+                    la += 1.0f - sg;
+                    const float dx = (-g) * (1.0f - sg) * sg;
+                    dp0 += dx;
+                    dk = -dx;
+                } else {
+                    const float x = o;
+                    la += fmaxf(x, 0.0f);
+                    const float dx = x >= 0.0f ? g : 0.0f;
+                    dp0 -= dx;
+                    dk = dx;
                 }
+                if (sub == k % LPU) dpm[k / LPU] = dk;
             }
         }
+        if (sub == 0) dpm[0] = dp0;
     }
 
     // ---- dz, list entries, planned partials ----------------------------------------
     if (kBackward) {
-        float dz[NP];
+        // each lane's own pairs; the list tasks (and the planned partial, pair 0) index dz by
+        // another pair: stage it through LDS.  A unit's lanes share one wave and a wave's LDS
+        // operations complete in order, so only the compiler must keep the reads after the
+        // writes (no workgroup barrier)
 #pragma unroll
-        for (int q = 0; q < NP; ++q) dz[q] = (dp[q] * (1.0f - p[q])) * p[q];
-        // the list tasks index dz by a lane-dependent pair: stage it through LDS
-        // (a register select chain is turned back into scratch by the compiler).  A
-        // unit's lanes share one wave and a wave's LDS operations complete in order, so
-        // only the compiler must keep the reads after the writes (no workgroup barrier)
-        if (sub == 0) {
-#pragma unroll
-            for (int q = 0; q < NP; ++q) ldz[ublk * NP + q] = dz[q];
+        for (int r = 0; r < R; ++r) {
+            const int q = sub + r * LPU;
+            if (q < NP) ldz[ublk * NP + q] = (dpm[r] * (1.0f - pm[r])) * pm[r];
         }
         static_assert(kWave % LPU == 0, "a unit's lanes must share a wave");
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -422,18 +484,19 @@ __device__ __forceinline__ void pairs_body(const PairsArgs &a, const int64_t blk
                 const int sl = __shfl(slot[t / LPU], ubase + (t % LPU));
                 const int q = t >> 1;
                 if (valid[q] && sl >= kCap && !(plan && t == 1)) {
+                    const float dzq = ldz[ublk * NP + q];
                     float o[EPL];
                     if (t & 1) {
                         const int64_t row = a.num_users + iid[q];
                         if constexpr (SC1) L::load_sc1(o, a.user_w, uid[q], D, sub);
                         else L::load(o, a.user_w, uid[q], D, sub);
-                        overflow_add<L>(a.hot_grad, row, D, sub, dz[q], o);
-                        if (sub == 0) fix_add(a.hot_bias_grad + row, dz[q]);
+                        overflow_add<L>(a.hot_grad, row, D, sub, dzq, o);
+                        if (sub == 0) fix_add(a.hot_bias_grad + row, dzq);
                     } else {
                         if constexpr (SC1) L::load_sc1(o, a.item_w, iid[q], D, sub);
                         else L::load(o, a.item_w, iid[q], D, sub);
-                        overflow_add<L>(a.hot_grad, uid[q], D, sub, dz[q], o);
-                        if (sub == 0) fix_add(a.hot_bias_grad + uid[q], dz[q]);
+                        overflow_add<L>(a.hot_grad, uid[q], D, sub, dzq, o);
+                        if (sub == 0) fix_add(a.hot_bias_grad + uid[q], dzq);
                     }
                 }
             }
@@ -442,13 +505,14 @@ __device__ __forceinline__ void pairs_body(const PairsArgs &a, const int64_t blk
         if (plan) {
             // block-level segmented sum of the positives' item-side rows, sorted by item
             const int stride = D + 1;
+            const float dz0 = ldz[ublk * NP];
             if (has_pos) {
 #pragma unroll
                 for (int e = 0; e < EPL; ++e) {
                     const int c = L::elem(sub, e);
-                    if (L::VEC || c < D) lrow[ublk * stride + c] = dz[0] * upos[e];
+                    if (L::VEC || c < D) lrow[ublk * stride + c] = dz0 * upos[e];
                 }
-                if (sub == 0) lrow[ublk * stride + D] = dz[0];
+                if (sub == 0) lrow[ublk * stride + D] = dz0;
             }
             if (sub == 0) lslot[ublk] = myslot;
             lds_barrier();
