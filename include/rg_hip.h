@@ -1039,6 +1039,70 @@ int rg_seq_pool_repr(void *stream, const float *E, int32_t dim, int64_t num_item
                      const int64_t *ptr, int32_t L, int64_t n, float *out);
 
 /* ------------------------------------------------------------------------------
+ * The causal-convolution sequence model (rg_seq_cnn.hip): stacked dilated causal convolutions
+ * over the item embeddings (spotlight/sequence/representations.py CNNNet of the reference; WaveNet,
+ * ByteNet).  Ids, padding, seq [B][L], neg [K][B][L], the mask, inv_count, the three losses and
+ * the [num_items][dim + 1] gradient buffer are rg_seq_pool_grads'; only the representation
+ * differs.  With e_p = E[s_p] (0 for p < 0 or a padded p), f tanh or relu, and layer l of width
+ * w_l, dilation D_l, weight W_l[j] (dim x dim, tap j = 0 .. w_l - 1) and bias c_l, for t = 0 .. L:
+ *     layer 0:     x0_t = f(c_0 + sum_j W_0[j] e_{t - 1 - (w_0 - 1 - j) D_0})  [+ e_{t-1}    if residual]
+ *     layer l > 0: xl_t = f(c_l + sum_j W_l[j] x(l-1)_{t - (w_l - 1 - j) D_l}) [+ x(l-1)_t   if residual]
+ * with x(l-1)_p = 0 for p < 0.  The score of item i at position t is b[i] + <x_t, E[i]> under the
+ * top layer's x_t; positions 0 .. L - 1 train and x_L serves.  A padded position inside a
+ * sequence is a zero input row; there is no count and no renormalisation.
+ *
+ * params is one flat fp32 vector (device): for each layer in order W_l as [w_l][dim in][dim out]
+ * (the reference's cnn_l.weight[out][in][j][0], transposed per tap), then c_l [dim];
+ * rg_seq_cnn_param_len floats.
+ *
+ * rg_seq_cnn_grads: forward, loss and backward of one step (3 num_layers + 3 launches: a
+ * convolution per layer, the scores with loss terms and dz, the loss, per layer the weight and the
+ * input gradient, and the reduction of the weight gradient).  grad has pooling's contract (zeroed
+ * on entry, float atomics, row 0 never written): the targets' and negatives' rows and, through
+ * layer 0, every item of a sequence.  param_grad [param_len] is WRITTEN, not accumulated: each
+ * slice of rows sums into its own copy and the copies are added in slice order, so for the same
+ * inputs it is the same bits on every run, as is the loss.  The convolutions and both gradient
+ * products run on the fp32 16x16x4 MFMA; tanh is tanhf.  workspace holds rg_seq_cnn_workspace_len
+ * floats, 16-byte aligned for the vector row layouts.
+ * RG_E_ARG (rg_last_error names the reason, no HIP call made, nothing written; the lengths are
+ * -1) on a null pointer, dim not a multiple of 16 in [16, 128], num_layers outside [1,
+ * RG_SEQ_CNN_MAX_LAYERS], a width outside [1, RG_SEQ_CNN_MAX_WIDTH], a dilation outside [1, 64],
+ * nonlinearity or residual outside {0, 1}, num_items outside [2, INT_MAX], L outside [1,
+ * RG_SEQ_MAX_LEN], K outside [1, RG_SEQ_MAX_NEG], B < 1 or B (L + 1) above INT_MAX - 15, a loss
+ * other than the three, or inv_count outside (0, 1].  An id outside [0, num_items) is read as
+ * padding.
+ *
+ * rg_seq_cnn_repr: out[r] = x_L of the top layer for the padded block ids [n][L], [n][dim]
+ * (device).  Each layer computes only the last positions the layers above reach, so a one-layer
+ * net needs no workspace (it may be null) and a deeper one rg_seq_cnn_repr_workspace_len floats.
+ * L == 0 gives x_0 (ids is not read); n == 0: RG_OK, no launch.  Refusals as above, L in [0,
+ * RG_SEQ_MAX_LEN].
+ *
+ * rg_seq_adam_flat: opt_update (torch.optim.Adam, coupled weight decay) element by element on a
+ * flat vector p [n] with moments m, v and gradient g (read only): the convolution parameters'
+ * half of the step.  RG_E_ARG on a null pointer, n < 0 or an optimizer other than Adam.
+ * ---------------------------------------------------------------------------- */
+#define RG_SEQ_CNN_MAX_LAYERS 4
+#define RG_SEQ_CNN_MAX_WIDTH 8
+struct rg_seq_cnn_t {
+    int32_t dim, num_layers, nonlinearity /* 0 tanh, 1 relu */, residual;
+    int32_t width[RG_SEQ_CNN_MAX_LAYERS], dilation[RG_SEQ_CNN_MAX_LAYERS];
+};
+typedef struct rg_seq_cnn_t rg_seq_cnn_t;
+int64_t rg_seq_cnn_param_len(const rg_seq_cnn_t *cfg);
+int64_t rg_seq_cnn_workspace_len(const rg_seq_cnn_t *cfg, int64_t B, int32_t L, int32_t K);
+int rg_seq_cnn_grads(void *stream, const rg_seq_cnn_t *cfg, const int64_t *seq, const int64_t *neg,
+                     const float *E, const float *b, const float *params, int64_t num_items, int64_t B,
+                     int32_t L, int32_t K, int32_t loss, float inv_count, float *grad, float *param_grad,
+                     float *workspace, float *loss_out);
+int64_t rg_seq_cnn_repr_workspace_len(const rg_seq_cnn_t *cfg, int64_t n, int32_t L);
+int rg_seq_cnn_repr(void *stream, const rg_seq_cnn_t *cfg, const float *E, const float *params,
+                    int64_t num_items, const int64_t *ids, int32_t L, int64_t n, float *workspace,
+                    float *out);
+int rg_seq_adam_flat(void *stream, float *p, float *m, float *v, const float *g, int64_t n,
+                     const rg_opt_t *opt);
+
+/* ------------------------------------------------------------------------------
  * MF fold-in (rg_mf_fold.hip): fit the rows and biases of users that were not in the training
  * set against FROZEN item tables -- no reference counterpart (the reference retrains).  One
  * launch, no workspace; item_w [num_items][dim] and item_b [num_items] are only read.

@@ -95,6 +95,15 @@ class Opt(ctypes.Structure):
                 ("bias_correction2_sqrt", ctypes.c_float)]
 
 
+SEQ_CNN_MAX_LAYERS, SEQ_CNN_MAX_WIDTH = 4, 8    # include/rg_hip.h RG_SEQ_CNN_MAX_LAYERS / _MAX_WIDTH
+
+
+class SeqCnn(ctypes.Structure):                 # rg_seq_cnn_t
+    _fields_ = [("dim", ctypes.c_int32), ("num_layers", ctypes.c_int32), ("nonlinearity", ctypes.c_int32),
+                ("residual", ctypes.c_int32), ("width", ctypes.c_int32 * SEQ_CNN_MAX_LAYERS),
+                ("dilation", ctypes.c_int32 * SEQ_CNN_MAX_LAYERS)]
+
+
 class MTGen(ctypes.Structure):
     _fields_ = [("state", ctypes.c_void_p), ("out", ctypes.c_void_p), ("state_before", ctypes.c_void_p),
                 ("nwords", ctypes.c_int64)]
@@ -418,6 +427,19 @@ SIGNATURES = [
     ("rg_seq_pool_repr", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
                                         ctypes.c_void_p]),
+    ("rg_seq_cnn_param_len", ctypes.c_int64, [ctypes.POINTER(SeqCnn)]),
+    ("rg_seq_cnn_workspace_len", ctypes.c_int64, [ctypes.POINTER(SeqCnn), ctypes.c_int64, ctypes.c_int32,
+                                                  ctypes.c_int32]),
+    ("rg_seq_cnn_grads", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SeqCnn), ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                        ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("rg_seq_cnn_repr_workspace_len", ctypes.c_int64, [ctypes.POINTER(SeqCnn), ctypes.c_int64, ctypes.c_int32]),
+    ("rg_seq_cnn_repr", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SeqCnn), ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
+                                       ctypes.c_void_p, ctypes.c_void_p]),
+    ("rg_seq_adam_flat", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(Opt)]),
     ("rg_als_long_row_len", ctypes.c_int32, []),
     ("rg_als_gram_workspace_len", ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32]),
     ("rg_als_gram", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_float,

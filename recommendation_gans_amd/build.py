@@ -23,9 +23,10 @@ SOURCES = ["rg_api.cpp", "rg_sampler.hip", "rg_mf.hip", "rg_mf_alt.hip", "rg_ste
            "rg_gan.hip", "rg_eval.hip", "rg_plan.hip",
            "rg_owner.hip", "rg_uniform.hip", "rg_membw.hip", "rg_pool.cpp", "rg_ncf_score.hip",
            "rg_mf_score.hip", "rg_mf_topk.hip", "rg_item_sim.hip", "rg_topk_wide.hip", "rg_gan_score.hip",
-           "rg_mf_fold.hip", "rg_cand.hip", "rg_diverse.hip", "rg_als.hip", "rg_seq.hip"]
+           "rg_mf_fold.hip", "rg_cand.hip", "rg_diverse.hip", "rg_als.hip", "rg_seq.hip",
+           "rg_seq_cnn.hip"]
 HEADERS = ["rg_common.h", "rg_gemm.h", "rg_mt.h", "rg_owner.h", "rg_mlp_update.h", "rg_mfma.h", "rg_mf_kernels.h",
-           "rg_stepper.h", "rg_mf_score_tile.h", "rg_topk_lists.h", "rg_topk_tiles.h", "rg_ncf.h"]
+           "rg_stepper.h", "rg_mf_score_tile.h", "rg_topk_lists.h", "rg_topk_tiles.h", "rg_ncf.h", "rg_seq.h"]
 # the two MF translation units share rg_mf_kernels.h, which -D defines reach: always built together;
 # likewise the NCF step's three (the host API and its two pair kernels, sharing rg_ncf.h)
 MF_UNIT = ("rg_mf.hip", "rg_mf_alt.hip")

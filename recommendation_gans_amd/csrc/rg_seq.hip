@@ -26,7 +26,7 @@
 // rounding, not to the bit.  The loss does not: a sequence's terms are summed by its own group in
 // position order into partial r, and one wave reduces the partials in a fixed order, in double.
 // Row 0 (padding) is never written.
-#include "rg_common.h"
+#include "rg_seq.h"
 
 #include <limits.h>
 
@@ -41,25 +41,6 @@ struct SeqArgs {
     float inv_count;
     float *grad, *dz, *partials;
 };
-
-// an id outside [0, num_items) is read as padding: no access outside the tables
-__device__ __forceinline__ int64_t safe_id(int64_t id, int64_t num_items) {
-    return (uint64_t)id < (uint64_t)num_items ? id : 0;
-}
-
-// grad[row] += dz * (x, 1): the row's dim elements from the lanes that own them, the bias
-// column from the group's first lane
-template <class L>
-__device__ __forceinline__ void emit_row(float *grad, int64_t row, int D, int sub, float dz,
-                                         const float (&x)[L::EPL]) {
-    float *g = grad + row * (int64_t)(D + 1);
-#pragma unroll
-    for (int e = 0; e < L::EPL; ++e) {
-        const int c = L::elem(sub, e);
-        if (c < D) unsafeAtomicAdd(g + c, dz * x[e]);
-    }
-    if (sub == 0) unsafeAtomicAdd(g + D, dz);
-}
 
 template <class L>
 __global__ void __launch_bounds__(kWave) seq_pool_grads_kernel(const SeqArgs a) {

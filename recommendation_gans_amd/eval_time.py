@@ -161,6 +161,13 @@ gather / cumsum / GEMM / topk -- on the same GPU in the same process, the two al
 steps at B in {256, 4096}, L in {10, 50}, d in {32, 64, 128}, bpr.  Device events, min / median, the
 largest difference of the two results, and the step's distance from max(gathered bytes at 8 TB/s,
 flops at the fp32 vector peak).  One JSON line per shape.
+
+    python -m recommendation_gans_amd.eval_time --metric seq_cnn [--items 26744] [--reps 20]
+
+times the causal-convolution sequence model the same way (rg_seq_cnn_grads + rg_seq_adam_dense +
+rg_seq_adam_flat, and one ``recommend_next`` block, against ``seq_engine.cnn_loss_torch`` with
+autograd and ``torch.optim.Adam``, and ``cnn_repr_torch`` / GEMM / topk), for the default net and a
+3-layer net of dilations 1 / 2 / 4, with the GEMM stages' bound (``main_seq_cnn``).
 """
 import argparse
 import contextlib
@@ -1258,6 +1265,132 @@ def main_seq_pool(args):
     return out
 
 
+def main_seq_cnn(args):
+    """``--metric seq_cnn``: one training step of the causal-convolution sequence model
+    (rg_seq_cnn_grads + rg_seq_adam_dense + rg_seq_adam_flat) and one recommend_next block against
+    the torch ops they replace, for the default net (w 3, 1 layer, tanh, residual) and a 3-layer
+    net (w 3, dilations 1 / 2 / 4).  ``gemm_bound_ms``: the three GEMM stages of every layer (the
+    convolution, the input gradient, the weight gradient: 2 R w d^2 flops each over R = B (L + 1)
+    rows) at the fp32 MFMA peak, against their compulsory traffic at 8 TB/s (per layer 9 R d floats:
+    the input read, x and y written, dx and y read twice, the input gradient written, the input read
+    again); ``grads_ms`` is rg_seq_cnn_grads alone, of which the GEMM stages are all but the score
+    and loss launches.  ``bound_ms`` of the step adds the dense Adam pass's 7 floats per parameter."""
+    from . import seq_engine
+    from .spotlight.sequence import ImplicitSequenceModel
+    from .spotlight.sequence.representations import CNNNet
+    dev = torch.device("cuda:0")
+    I, lr = args.items, 1e-2
+    nets = (("w3", dict(kernel_width=3, dilation=1, num_layers=1)),
+            ("w3x3_d124", dict(kernel_width=3, dilation=(1, 2, 4), num_layers=3)))
+    out = []
+    for d in (32, 64, 128):
+        for name, kw in nets:
+            torch.manual_seed(d)
+            net = CNNNet(I, embedding_dim=d, **kw)
+            cfg = seq_engine.cnn_config_of(net)
+            E0 = net.item_embeddings.weight.data.clone()
+            p0 = seq_engine.cnn_pack(cfg, [(c.weight.data, c.bias.data) for c in net.cnn_layers])
+            wd2 = sum(cfg.width[l] for l in range(cfg.num_layers)) * d * d
+            for B in (256, 4096):
+                for L in (10, 50):
+                    rs = np.random.RandomState(B + L + d)
+                    seq = torch.from_numpy(rs.randint(1, I, (B, L))).to(dev)
+                    seq[: B // 4, : L // 2] = 0
+                    neg = torch.from_numpy(rs.randint(0, I, (1, B, L))).to(dev)
+                    count = int((seq != 0).sum())
+                    E, b, p = E0.to(dev).clone(), torch.zeros(I, device=dev), p0.to(dev).clone()
+                    mom = [torch.zeros_like(E), torch.zeros_like(E), torch.zeros_like(b), torch.zeros_like(b)]
+                    pmom = [torch.zeros_like(p), torch.zeros_like(p)]
+                    grad, pg = torch.zeros(I, d + 1, device=dev), torch.zeros_like(p)
+                    ws = seq_engine.cnn_workspace(cfg, B, L, 1, dev)
+                    Et, bt, pt = (x.clone().requires_grad_(True) for x in (E, b, p))
+                    opt = torch.optim.Adam([Et, bt, pt], lr=lr)
+
+                    def grads():
+                        return seq_engine.cnn_grads(cfg, E, b, p, seq, neg, "bpr", grad=grad, mask_count=count,
+                                                    checked=True, param_grad=pg, workspace=ws)[0]
+
+                    def new():
+                        lv = grads()
+                        seq_engine.adam_dense(E, b, *mom, grad, 1, lr)
+                        seq_engine.adam_flat(p, *pmom, pg, 1, lr)
+                        return lv
+
+                    def old():
+                        opt.zero_grad(set_to_none=True)
+                        lv = seq_engine.cnn_loss_torch(cfg, Et, bt, pt, seq, neg, "bpr")
+                        lv.backward()
+                        with torch.no_grad():
+                            Et.grad[0] = 0
+                            bt.grad[0] = 0
+                        opt.step()
+                        return lv.detach()
+
+                    lv_new, g_new, pg_new = seq_engine.cnn_grads(cfg, E, b, p, seq, neg, "bpr", mask_count=count,
+                                                                 checked=True)
+                    lv_old = seq_engine.cnn_loss_torch(cfg, Et, bt, pt, seq, neg, "bpr")
+                    gE, gb, gp = torch.autograd.grad(lv_old, [Et, bt, pt])
+                    gE[0] = 0
+                    gb[0] = 0
+                    diff = float(max((g_new[:, :d] - gE).abs().max(), (g_new[:, d] - gb).abs().max(),
+                                     (pg_new - gp).abs().max()))
+                    loss_diff = abs(float(lv_new) - float(lv_old.detach()))
+                    for _ in range(3):
+                        new(), old()
+                    t_new, t_old, t_grads = [], [], []
+                    for _ in range(args.reps):
+                        t_new += timed(new, 1)
+                        t_old += timed(old, 1)
+                    for _ in range(args.reps):      # the gradient call alone; the Adam passes zero grad
+                        t_grads += timed(grads, 1)
+                        seq_engine.adam_dense(E, b, *mom, grad, 1, lr)
+                    R = B * (L + 1)
+                    gemm = max(6.0 * R * wd2 / PEAK_FP32_MFMA, 9.0 * R * d * cfg.num_layers * 4 / PEAK_HBM) * 1e3
+                    bound = gemm + 7.0 * (I * (d + 1) + p.numel()) * 4 / PEAK_HBM * 1e3
+                    r = {"metric": "seq_cnn", "workload": "train_step", "net": name, "dim": d, "B": B, "L": L,
+                         "items": I, "loss": "bpr", "reps": args.reps, "kernel_ms": stats(t_new),
+                         "torch_ms": stats(t_old), "grads_ms": stats(t_grads),
+                         "median_ratio_torch_over_kernel": float(np.median(t_old) / np.median(t_new)),
+                         "max_abs_grad_diff": diff, "abs_loss_diff": loss_diff, "gemm_gflop": 6.0 * R * wd2 / 1e9,
+                         "gemm_bound_ms": gemm, "gemm_bound_share_of_grads": float(gemm / np.median(t_grads)),
+                         "bound_ms": bound, "kernel_over_bound": float(np.median(t_new) / bound)}
+                    print(json.dumps(r), flush=True)
+                    out.append(r)
+                    del opt, Et, bt, pt, E, b, p, mom, pmom, grad, pg, ws
+            # serving: one recommend_next block of 4096 sequences of 50 items, k = 10
+            model = ImplicitSequenceModel(representation=net)
+            model.set_tables(E0, torch.zeros(I), device=dev)
+            rs = np.random.RandomState(d)
+            seqs = rs.randint(1, I, (4096, 50))
+            seq_dev = torch.from_numpy(seqs).to(dev)
+
+            def new_rec():
+                return model.recommend_next(seqs, 10)
+
+            def old_rec():
+                rL = seq_engine.cnn_repr_torch(cfg, model.item_embeddings, model._conv, seq_dev)
+                blk = rL @ model.item_embeddings.T + model.item_biases[None, :]
+                blk[:, 0] = float("-inf")
+                blk.scatter_(1, seq_dev, float("-inf"))
+                return torch.topk(blk, 10, dim=1).indices.cpu().numpy()
+
+            for _ in range(2):
+                a, c = new_rec(), old_rec()
+            t_new, t_old = [], []
+            for _ in range(args.reps):
+                t_new += timed(new_rec, 1)
+                t_old += timed(old_rec, 1)
+            r = {"metric": "seq_cnn", "workload": "recommend_next", "net": name, "dim": d, "sequences": 4096, "L": 50,
+                 "items": I, "k": 10, "reps": args.reps, "kernel_ms": stats(t_new), "torch_ms": stats(t_old),
+                 "median_ratio_torch_over_kernel": float(np.median(t_old) / np.median(t_new)),
+                 "rows_with_other_ids": int((a != c).any(axis=1).sum())}
+            print(json.dumps(r), flush=True)
+            out.append(r)
+            del model
+            torch.cuda.empty_cache()
+    return out
+
+
 def main_scores(args):
     """The default mode: one block of ``--users`` users against every item, NCFEngine.score_users
     (rg_ncf_score_users) against the pairwise NCFEngine.scores_torch."""
@@ -1307,7 +1440,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--metric", choices=("scores", "mrr", "slates", "pairs", "mf_scores", "mf_topk", "item_sim",
                                         "gan_recommend", "topk_wide", "gan_score", "fold_in", "candidates", "mmr",
-                                        "als", "seq_pool"),
+                                        "als", "seq_pool", "seq_cnn"),
                     default="scores")
     ap.add_argument("--batch", type=int, default=8192)
     ap.add_argument("--users", type=int, default=None)
@@ -1327,7 +1460,8 @@ def main(argv=None):
             "mf_scores": main_mf_scores, "mf_topk": main_mf_topk, "item_sim": main_item_sim,
             "gan_recommend": main_gan_recommend, "topk_wide": main_topk_wide,
             "gan_score": main_gan_score, "fold_in": main_fold_in, "candidates": main_candidates,
-            "mmr": main_mmr, "als": main_als, "seq_pool": main_seq_pool}[args.metric](args)
+            "mmr": main_mmr, "als": main_als, "seq_pool": main_seq_pool,
+            "seq_cnn": main_seq_cnn}[args.metric](args)
 
 
 if __name__ == "__main__":

@@ -1,6 +1,9 @@
-"""ImplicitSequenceModel (spotlight/sequence/implicit.py of the reference) for the pooling
-representation: a session is the mean of the items seen so far (PoolNet, representations.py;
-Covington et al. 2016), the next item is scored b[i] + <r, E[i]>.
+"""ImplicitSequenceModel (spotlight/sequence/implicit.py of the reference) for two
+representations.  ``representation='pooling'``: a session is the mean of the items seen so far
+(PoolNet; Covington et al. 2016).  ``representation=<a representations.CNNNet>``: stacked causal
+dilated convolutions over the items seen so far (the reference's own way to configure widths and
+dilations); the net gives the configuration, ``embedding_dim``, ``num_items`` and the initial
+parameters.  Either way the next item is scored b[i] + <r, E[i]>.
 
 The constructor, ``fit`` and ``predict`` keep the reference's signatures.  What differs, on purpose:
   * the reference's class cannot run (its ``sample_items`` call no longer matches sampling.py), so
@@ -8,7 +11,8 @@ The constructor, ``fit`` and ``predict`` keep the reference's signatures.  What 
     backward in one launch, torch's dense Adam in a second (rg_seq_adam_dense);
   * ``loss='pointwise'`` is refused: the reference's pointwise loss takes probabilities and drops
     the mask;
-  * only ``representation='pooling'`` and the default Adam exist (NotImplementedError otherwise);
+  * only ``'pooling'``, a ``CNNNet`` instance and the default Adam exist (NotImplementedError
+    otherwise: the strings 'cnn', 'lstm' and 'mixture' among them);
   * negatives come from ``sampling.sample_items(..., device=)``: NumPy's ids, bit for bit, drawn on
     the GPU, the model's RandomState advanced as NumPy advances it.
 Serving on top: ``predict_batch`` (a device score block), ``recommend_next`` (top-k, preceding
@@ -19,6 +23,7 @@ import torch
 
 from ... import _lib, seq_engine
 from ..layers import ScaledEmbedding, ZeroEmbedding
+from .representations import CNNNet
 from ..sampling import sample_items
 from ..torch_utils import shuffle
 
@@ -31,8 +36,16 @@ class ImplicitSequenceModel:
                  learning_rate=1e-2, optimizer_func=None, use_cuda=True, sparse=False, random_state=None,
                  num_negative_samples=5):
         seq_engine.check_loss(loss)
-        if representation != "pooling":
-            raise NotImplementedError(f"representation {representation!r}: only 'pooling' is implemented")
+        self._net = self._cnn = None
+        if isinstance(representation, CNNNet):
+            self._net, self._cnn = representation, seq_engine.cnn_config_of(representation)
+            embedding_dim = representation.embedding_dim
+        elif isinstance(representation, str) and representation == "cnn":
+            raise NotImplementedError("representation 'cnn': pass a representations.CNNNet instance, which carries "
+                                      "the widths, dilations and initial parameters")
+        elif not (isinstance(representation, str) and representation == "pooling"):
+            raise NotImplementedError(f"representation {representation!r}: only 'pooling' and a CNNNet instance "
+                                      f"are implemented")
         if optimizer_func is not None:
             raise NotImplementedError("optimizer_func: the fused step runs torch.optim.Adam's update only")
         seq_engine.check_dim(int(embedding_dim))
@@ -55,7 +68,8 @@ class ImplicitSequenceModel:
         self._E = self._b = None
 
     def __repr__(self):
-        return "<{}: pooling, d = {}>".format(self.__class__.__name__, self._embedding_dim)
+        return "<{}: {}, d = {}>".format(self.__class__.__name__, "cnn" if self._cnn else "pooling",
+                                         self._embedding_dim)
 
     @property
     def _initialized(self):
@@ -67,12 +81,21 @@ class ImplicitSequenceModel:
         self._num_items = int(interactions.num_items)
         if self._num_items < 2:
             raise ValueError("the model needs at least one item beside the padding id 0")
+        if self._net is not None:
+            if self._net.num_items != self._num_items:
+                raise ValueError("the net was built for {} items, the interactions hold {}".format(
+                    self._net.num_items, self._num_items))
+            self.set_tables(self._net.item_embeddings.weight.data, self._net.item_biases.weight.data.reshape(-1),
+                            device=dev)
+            return
         E = ScaledEmbedding(self._num_items, self._embedding_dim, padding_idx=PADDING_IDX).weight.data
         b = ZeroEmbedding(self._num_items, 1, padding_idx=PADDING_IDX).weight.data.reshape(-1)
         self.set_tables(E, b, device=dev)
 
-    def set_tables(self, E, b, device=None):
-        """Start from the given tables (row 0 must be zero); the Adam state starts over."""
+    def set_tables(self, E, b, conv=None, device=None):
+        """Start from the given tables (row 0 must be zero); the Adam state starts over.  With a
+        CNNNet, ``conv`` is the flat vector of the convolutions' parameters
+        (``seq_engine.cnn_pack``); None: the net's own current ones."""
         _lib.require_gpu()
         dev = torch.device(device if device is not None else "cuda")
         E = torch.as_tensor(E, dtype=torch.float32)
@@ -87,6 +110,29 @@ class ImplicitSequenceModel:
                          torch.zeros_like(self._b), torch.zeros_like(self._b)]
         self._grad = torch.zeros(self._num_items, self._embedding_dim + 1, dtype=torch.float32, device=dev)
         self._step = 0
+        if self._cnn is None:
+            if conv is not None:
+                raise ValueError("conv: the pooling representation has no convolution parameters")
+            return
+        if conv is None:
+            conv = seq_engine.cnn_pack(self._cnn, [(c.weight.data, c.bias.data) for c in self._net.cnn_layers])
+        conv = torch.as_tensor(conv, dtype=torch.float32).reshape(-1)
+        if conv.numel() != seq_engine.cnn_param_len(self._cnn):
+            raise ValueError("conv must hold {} floats".format(seq_engine.cnn_param_len(self._cnn)))
+        self._conv = conv.to(dev).contiguous().clone()
+        self._conv_moments = [torch.zeros_like(self._conv), torch.zeros_like(self._conv)]
+        self._conv_grad = torch.zeros_like(self._conv)
+        self._conv_ws = self._conv_ws_shape = None
+
+    def conv_state_dict(self):
+        """The convolutions' parameters in the reference's layout: {'cnn_i.weight': [d, d, w, 1],
+        'cnn_i.bias': [d]} on the host."""
+        if self._cnn is None or not self._initialized:
+            raise RuntimeError("no convolution parameters: the model is not an initialised CNN model")
+        out = {}
+        for i, (W, c) in enumerate(seq_engine.cnn_unpack(self._cnn, self._conv.cpu())):
+            out["cnn_{}.weight".format(i)], out["cnn_{}.bias".format(i)] = W.contiguous().clone(), c.clone()
+        return out
 
     @property
     def item_embeddings(self):
@@ -105,7 +151,8 @@ class ImplicitSequenceModel:
 
     def train_batch(self, batch, mask_count=None):
         """One step on a device block of sequences [B, L] whose ids were checked: the negatives'
-        draw, rg_seq_pool_grads, rg_seq_adam_dense.  Returns the loss as a 0-d device tensor."""
+        draw, rg_seq_pool_grads (a CNNNet: rg_seq_cnn_grads), rg_seq_adam_dense (and
+        rg_seq_adam_flat on the convolutions).  Returns the loss as a 0-d device tensor."""
         B, L = (int(x) for x in batch.shape)
         K = self._num_negative_samples
         if mask_count is None:
@@ -114,12 +161,23 @@ class ImplicitSequenceModel:
             raise ValueError("the batch holds padding only (mask.sum() == 0)")
         neg = sample_items(None, None, self._num_items, (K * B, L), random_state=self._random_state,
                            device=self._E.device).view(K, B, L)
-        loss, _ = seq_engine.pool_grads(self._E, self._b, batch, neg, self._loss, grad=self._grad,
-                                        mask_count=mask_count, checked=True)
+        if self._cnn is None:
+            loss, _ = seq_engine.pool_grads(self._E, self._b, batch, neg, self._loss, grad=self._grad,
+                                            mask_count=mask_count, checked=True)
+        else:
+            if self._conv_ws is None or self._conv_ws_shape != (B, L, K):      # kept between steps of one shape
+                self._conv_ws = seq_engine.cnn_workspace(self._cnn, B, L, K, self._E.device)
+                self._conv_ws_shape = (B, L, K)
+            loss, _, _ = seq_engine.cnn_grads(self._cnn, self._E, self._b, self._conv, batch, neg, self._loss,
+                                              grad=self._grad, mask_count=mask_count, checked=True,
+                                              param_grad=self._conv_grad, workspace=self._conv_ws)
         self._step += 1
         mE, vE, mb, vb = self._moments
         seq_engine.adam_dense(self._E, self._b, mE, vE, mb, vb, self._grad, self._step, self._learning_rate,
                               weight_decay=self._l2)
+        if self._cnn is not None:
+            seq_engine.adam_flat(self._conv, *self._conv_moments, self._conv_grad, self._step, self._learning_rate,
+                                 weight_decay=self._l2)
         return loss
 
     def fit(self, interactions, verbose=False):
@@ -157,12 +215,16 @@ class ImplicitSequenceModel:
 
     def predict_batch(self, sequences):
         """Raw next-item scores of every item for a block of sequences [n, L]: a float32
-        [n, num_items] block on the device (rg_seq_pool_repr, rg_mf_score_users_raw)."""
+        [n, num_items] block on the device (rg_seq_pool_repr or rg_seq_cnn_repr, then
+        rg_mf_score_users_raw)."""
         _, seq_dev = self._sequences_dev(sequences)
         return self._scores(seq_dev)
 
     def _scores(self, seq_dev):
-        R = seq_engine.pool_repr(self._E, seq_dev, checked=True)
+        if self._cnn is not None:
+            R = seq_engine.cnn_repr(self._cnn, self._E, self._conv, seq_dev, checked=True)
+        else:
+            R = seq_engine.pool_repr(self._E, seq_dev, checked=True)
         return seq_engine.score_block_raw(R, self._E, self._b)
 
     def predict(self, sequences, item_ids=None):
